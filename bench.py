@@ -8,7 +8,7 @@ rank=64 implicit 100M users x 10M items at 1/2/4/8 GPU". Weak scaling:
 random-init factors (there is no network for datasets).
 
 Launch (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   # N>1 via: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #   --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -16,6 +16,11 @@ One step = one full ALS iteration (user half-step + item half-step), each
 half-step = RCCL all-gather of the fixed factor side + one fused HIP
 Gramian+Cholesky solve over the local row block. Nothing is skipped inside
 the timed region (both collectives + both solves + YtY GEMMs). fp32 compute.
+
+A plain run only sets up, warms up, times the K steps and prints the JSON
+result line. --dump-outputs DIR additionally writes what the last timed step
+computed as DIR/<name>.npy; --full additionally co-measures the config-5
+serve metric after a train-mode run (reported under `extra_metrics`).
 """
 
 from __future__ import annotations
@@ -26,7 +31,12 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
+
+# --dump-outputs budget: 64 MB over all files. A factor matrix larger than
+# its share is written as a fixed, seeded sample of whole rows.
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
 
 
 def log(msg):
@@ -55,6 +65,28 @@ def synth_shard(trainer, nnz_per_user: int, seed: int, device):
     it_u, it_i, it_v = pdist.exchange_triples(g_users, items, vals,
                                               trainer.n_items)
     return (users, items, vals), (it_i, it_u, it_v)
+
+
+def sample_rows(n_rows: int, max_rows: int, seed: int):
+    """Sorted row ids to dump: all rows when they fit, else a seeded
+    sample without replacement (the same ids for the same arguments)."""
+    if n_rows <= max_rows:
+        return np.arange(n_rows, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    return np.sort(rng.choice(n_rows, size=max_rows, replace=False))
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each array as <out_dir>/<name>.npy (float32 or float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= DUMP_BUDGET_BYTES, total
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}")
 
 
 def run_train(args, device):
@@ -104,6 +136,20 @@ def run_train(args, device):
         pt = trainer.phase_times
         log(f"phase times over timed steps: gather {pt['gather_s']:.3f}s "
             f"solve {pt['solve_s']:.3f}s")
+    if args.dump_outputs and pdist.get_rank() == 0:
+        # the factors a caller of step() reads back after the last timed
+        # iteration (this rank's row blocks). Row ids ride along as
+        # float64 so a sampled dump says which rows it holds.
+        arrays = {}
+        per_row = args.rank * 4 + 8
+        for name, fac, sd in (("user_factors", trainer.X, args.seed),
+                              ("item_factors", trainer.Y, args.seed + 1)):
+            rows = sample_rows(fac.shape[0],
+                               DUMP_BUDGET_BYTES // 2 // per_row, sd)
+            idx = torch.from_numpy(rows).to(device)
+            arrays[name] = fac.index_select(0, idx).float().cpu().numpy()
+            arrays[name + "_rows"] = rows.astype(np.float64)
+        dump_outputs(args.dump_outputs, arrays)
     total_nnz = args.users_per_gpu * args.nnz_per_user * world
     value = total_nnz / sec_per_iter  # ratings solved per second per iter
     return value, sec_per_iter, {
@@ -152,12 +198,23 @@ def run_serve(args, device):
     for _ in range(args.warmup):
         one_batch()
     sync()
+    res = None
     t0 = time.time()
     for _ in range(args.steps):
-        one_batch()
+        res = one_batch()
     sync()
     elapsed = pdist.max_scalar(time.time() - t0)
     sec_per_batch = elapsed / args.steps
+    if args.dump_outputs and pdist.get_rank() == 0 and res is not None:
+        # the (values, global item ids) of the last timed batch; ids as
+        # float64 (exact), -1 marks an unfilled slot
+        rows = torch.from_numpy(sample_rows(
+            B, DUMP_BUDGET_BYTES // (K * 12), args.seed)).to(device)
+        dump_outputs(args.dump_outputs, {
+            "topk_values": res[0].index_select(0, rows).float().cpu().numpy(),
+            "topk_indices": res[1].index_select(0, rows).double().cpu()
+            .numpy(),
+        })
     value = B / sec_per_batch  # user-queries served per second (whole job)
     return value, sec_per_batch, {
         "model": f"als_rank{args.rank}_topk_serving",
@@ -184,8 +241,15 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cpu-small", action="store_true",
                     help="tiny CPU config for smoke testing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as "
+                         "DIR/<name>.npy (float32/float64, <= 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (train mode: the co-measured serve metric)")
     ap.add_argument("--no-serve-extra", action="store_true",
-                    help="skip the co-measured serve metric in train mode")
+                    help="with --full: skip the co-measured serve metric "
+                         "in train mode")
     args = ap.parse_args()
 
     if args.cpu_small:
@@ -217,12 +281,13 @@ def main():
         value, spi, config = run_train(args, device)
         metric = "als_ratings_per_sec"
         unit = "ratings/s"
-        # co-measure the config-5 serve metric OUTSIDE the timed train
-        # region so driver-run records certify serving too (VERDICT r1
+        # --full: co-measure the config-5 serve metric OUTSIDE the timed
+        # train region so such records certify serving too (VERDICT r1
         # item 6); skipped on CPU smoke runs to stay fast
-        if use_cuda and not args.no_serve_extra:
+        if args.full and use_cuda and not args.no_serve_extra:
             sargs = argparse.Namespace(**vars(args))
             sargs.steps, sargs.warmup = 5, 2
+            sargs.dump_outputs = None
             sval, sspb, sconf = run_serve(sargs, device)
             extra = {
                 "serving_queries_per_sec": sval,
