@@ -22,14 +22,18 @@ extern "C" void launch_topk_score(
     const long long* ban_indptr, const int* ban_indices,
     float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
-    unsigned long long* prof, hipStream_t stream);
+    unsigned long long* prof,
+    const int* item_cats, const int* query_cats, int cw,
+    hipStream_t stream);
 
 extern "C" void launch_topk_mfma(
     const unsigned short* Xq, const unsigned short* Y,
     const uint8_t* item_mask, const long long* ban_indptr,
     const int* ban_indices, float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
-    unsigned long long* prof, unsigned* th_g, hipStream_t stream);
+    unsigned long long* prof, unsigned* th_g,
+    const int* item_cats, const int* query_cats, int cw,
+    hipStream_t stream);
 
 namespace {
 
@@ -41,6 +45,33 @@ void check_cuda_f32(const torch::Tensor& t, const char* name) {
 
 bool supported_rank(int64_t f) {
   return f == 16 || f == 32 || f == 64 || f == 128;
+}
+
+// Optional per-query category filter: item_cats [N, W] and query_cats
+// [B, W] int32 bit words, W in {1, 2, 4}, given together or not at all.
+// Returns W (0 = no filter); any mismatch raises.
+int check_cats(const c10::optional<torch::Tensor>& item_cats,
+               const c10::optional<torch::Tensor>& query_cats,
+               int64_t B, int64_t N, bool has_prof) {
+  TORCH_CHECK(item_cats.has_value() == query_cats.has_value(),
+              "item_cats and query_cats must be given together");
+  if (!item_cats.has_value()) return 0;
+  TORCH_CHECK(!has_prof, "prof cannot be combined with category filters");
+  TORCH_CHECK(item_cats->is_cuda() && item_cats->is_contiguous() &&
+                  item_cats->scalar_type() == torch::kInt32 &&
+                  item_cats->dim() == 2,
+              "item_cats must be a contiguous [N, W] i32 GPU tensor");
+  TORCH_CHECK(query_cats->is_cuda() && query_cats->is_contiguous() &&
+                  query_cats->scalar_type() == torch::kInt32 &&
+                  query_cats->dim() == 2,
+              "query_cats must be a contiguous [B, W] i32 GPU tensor");
+  const int64_t W = item_cats->size(1);
+  TORCH_CHECK(W == 1 || W == 2 || W == 4,
+              "category words W must be 1, 2 or 4, got ", W);
+  TORCH_CHECK(item_cats->size(0) == N, "item_cats must have N rows");
+  TORCH_CHECK(query_cats->size(0) == B && query_cats->size(1) == W,
+              "query_cats must be [B, W] with item_cats' W");
+  return (int)W;
 }
 
 // Solve one ALS half-iteration: for every CSR row r,
@@ -128,7 +159,9 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
     c10::optional<torch::Tensor> item_mask,
     c10::optional<torch::Tensor> ban_indptr,
     c10::optional<torch::Tensor> ban_indices, int64_t item_base,
-    c10::optional<torch::Tensor> prof) {
+    c10::optional<torch::Tensor> prof,
+    c10::optional<torch::Tensor> item_cats,
+    c10::optional<torch::Tensor> query_cats) {
   check_cuda_f32(Xq, "Xq");
   check_cuda_f32(Y, "Y");
   const int64_t f = Y.size(1);
@@ -138,6 +171,9 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   TORCH_CHECK(n_slices >= 1);
+  const int cw = check_cats(item_cats, query_cats, B, N, prof.has_value());
+  const int* ic_ptr = cw ? item_cats->data_ptr<int>() : nullptr;
+  const int* qc_ptr = cw ? query_cats->data_ptr<int>() : nullptr;
   const uint8_t* mask_ptr = nullptr;
   if (item_mask.has_value()) {
     TORCH_CHECK(item_mask->is_cuda() && item_mask->is_contiguous() &&
@@ -176,7 +212,8 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
   launch_topk_score(Xq.data_ptr<float>(), Y.data_ptr<float>(), mask_ptr,
                     bi_ptr, bx_ptr, out_val.data_ptr<float>(),
                     out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f,
-                    (int)K, (int)n_slices, (int)item_base, prof_ptr, stream);
+                    (int)K, (int)n_slices, (int)item_base, prof_ptr, ic_ptr,
+                    qc_ptr, cw, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }
@@ -189,7 +226,9 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
     c10::optional<torch::Tensor> item_mask,
     c10::optional<torch::Tensor> ban_indptr,
     c10::optional<torch::Tensor> ban_indices, int64_t item_base,
-    c10::optional<torch::Tensor> prof) {
+    c10::optional<torch::Tensor> prof,
+    c10::optional<torch::Tensor> item_cats,
+    c10::optional<torch::Tensor> query_cats) {
   TORCH_CHECK(Xq.is_cuda() && Xq.is_contiguous() &&
                   Xq.scalar_type() == torch::kBFloat16,
               "Xq must be contiguous bf16 GPU");
@@ -204,6 +243,9 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   TORCH_CHECK(n_slices >= 1);
+  const int cw = check_cats(item_cats, query_cats, B, N, prof.has_value());
+  const int* ic_ptr = cw ? item_cats->data_ptr<int>() : nullptr;
+  const int* qc_ptr = cw ? query_cats->data_ptr<int>() : nullptr;
   const uint8_t* mask_ptr = nullptr;
   if (item_mask.has_value()) {
     TORCH_CHECK(item_mask->is_cuda() && item_mask->is_contiguous() &&
@@ -263,7 +305,7 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
       reinterpret_cast<const unsigned short*>(Y.data_ptr()), mask_ptr,
       bi_ptr, bx_ptr, out_val.data_ptr<float>(), out_idx.data_ptr<int>(),
       (int)B, (long long)N, (int)f, (int)K, (int)n_slices, (int)item_base,
-      prof_ptr, th_g_ptr, stream);
+      prof_ptr, th_g_ptr, ic_ptr, qc_ptr, cw, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }
@@ -283,11 +325,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
-        py::arg("prof") = py::none());
+        py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
+        py::arg("query_cats") = py::none());
   m.def("topk_score_mfma", &topk_score_mfma,
         "Fused masked top-K scoring on MFMA (bf16 in, fp32 accumulate)",
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
-        py::arg("prof") = py::none());
+        py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
+        py::arg("query_cats") = py::none());
 }

@@ -59,7 +59,16 @@ __device__ __forceinline__ bool in_sorted(const int* arr, int n, int x) {
 // staging / score+insert / writeback), summed per workgroup into
 // prof[5] = {setup, stage, score, write, blocks}. The live serving path
 // launches the PROF=false instantiation — zero probe cost.
-template <int F, bool PROF>
+//
+// CW = category words per item/query (0 = no category filter). With
+// CW > 0 item j is a candidate for query b iff
+//   OR_w (item_cats[j,w] & query_cats[b,w]) != 0;
+// the chunk's TK_CHUNK x CW words are staged into LDS with the Y rows,
+// each user's CW accepted words sit in LDS too, and a filtered score
+// becomes -FLT_MAX BEFORE the threshold test (see topk_mfma.hip for why
+// the filter must not wait for the insert path). All CW > 0 code sits
+// under `if constexpr`; CW == 0 is unchanged.
+template <int F, bool PROF, int CW = 0>
 __global__ __launch_bounds__(256, 3) void topk_score_kernel(
     const float* __restrict__ Xq,        // B x F query vectors
     const float* __restrict__ Y,         // N x F item factors
@@ -69,14 +78,22 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
     float* __restrict__ out_val,         // B x (n_slices*TK_WAVES) x K
     int* __restrict__ out_idx,
     int B, long long N, int K, int n_slices, int item_base,
-    unsigned long long* prof)
+    unsigned long long* prof,
+    const int* __restrict__ item_cats,    // N x CW bit words (CW > 0)
+    const int* __restrict__ query_cats)   // B x CW accepted-bit words
 {
+  static_assert(CW == 0 || CW == 1 || CW == 2 || CW == 4,
+                "category words per item must be 1, 2 or 4");
+  static_assert(CW == 0 || !PROF, "no phase probe with the category filter");
   constexpr int FP = F + 4;  // row stride: 16B-aligned so the score loop
                              // reads ys rows as ds_read_b128 quads
-  // dynamic LDS: ys[TK_CHUNK][FP] | topv[TK_WAVES*TK_UPB][K] | topi[...]
+  // dynamic LDS: ys[TK_CHUNK][FP] | cats[TK_CHUNK][CW] | qc[CW][TK_UPB] |
+  //              topv[TK_WAVES*TK_UPB][K] | topi[...]
   extern __shared__ float lds[];
   float* ys = lds;
-  float* topv = ys + TK_CHUNK * FP;
+  unsigned* cats_lds = reinterpret_cast<unsigned*>(ys + TK_CHUNK * FP);
+  unsigned* qc_lds = cats_lds + TK_CHUNK * CW;   // [CW][TK_UPB]
+  float* topv = ys + TK_CHUNK * FP + TK_CHUNK * CW + TK_UPB * CW;
   int* topi = reinterpret_cast<int*>(topv + TK_WAVES * TK_UPB * (K + 1));
 
   const int tid = threadIdx.x;
@@ -148,6 +165,20 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
     ban = ban_indices + b0;
   }
 
+  // each user's accepted-category words, loaded once, word-major
+  // [CW][TK_UPB] in LDS: the kernel sits at its VGPR cap (F >= 64 spilled
+  // with the words held in registers), and lane = user makes the read
+  // conflict-free. A lane without a user stores zero, which filters
+  // everything. Written by wave 0, read after the chunk loop's barriers.
+  if constexpr (CW > 0) {
+    if (wave == 0) {
+#pragma unroll
+      for (int w = 0; w < CW; ++w)
+        qc_lds[w * TK_UPB + lane] =
+            has_user ? (unsigned)query_cats[guser * CW + w] : 0u;
+    }
+  }
+
   // Item staging is software-pipelined through registers: while chunk i
   // is scored out of LDS, chunk i+1's global loads are already in flight
   // into stg[] (the phase probe measured un-overlapped staging at 33.6%
@@ -161,6 +192,15 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
   constexpr int SREG4 = Q4 >= 256 ? Q4 / 256 : 1;
   constexpr bool PIPE = (F <= 64);
   f32x4 stg4[PIPE ? SREG4 : 1];
+  // category words ride the same pipeline: the chunk's TK_CHUNK*CW words
+  // are contiguous in global memory, thread t < TK_CHUNK*CW carries word
+  // t (rows past the slice end stage 0 = "filtered")
+  unsigned cstg = 0u;
+  if constexpr (CW > 0) {
+    if (PIPE && tid < TK_CHUNK * CW)
+      cstg = (it0 + tid / CW < it1)
+          ? (unsigned)item_cats[it0 * CW + tid] : 0u;
+  }
   if (PIPE) {
     const int cn0 = (int)min((long long)TK_CHUNK, it1 - it0);
     // uniform chunk base folded into the pointer: the per-thread offset
@@ -198,12 +238,20 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
           dst[3] = stg4[r].w;
         }
       }
+      if constexpr (CW > 0) {
+        if (tid < TK_CHUNK * CW) cats_lds[tid] = cstg;
+      }
     } else {
       // coalesced stage of cn item rows
       for (int e = tid; e < cn * F; e += 256) {
         const int c = e / F;
         const int k = e % F;
         ys[c * FP + k] = Y[(base + c) * F + k];
+      }
+      if constexpr (CW > 0) {
+        if (tid < TK_CHUNK * CW)
+          cats_lds[tid] = (tid / CW < cn)
+              ? (unsigned)item_cats[base * CW + tid] : 0u;
       }
     }
     __syncthreads();
@@ -214,6 +262,11 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
       // barrier wait" signature). Here they fly under the score loop
       // and are awaited by the next iteration's first barrier.
       const long long nbase = base + TK_CHUNK;
+      if constexpr (CW > 0) {
+        if (nbase < it1 && tid < TK_CHUNK * CW)
+          cstg = (nbase + tid / CW < it1)
+              ? (unsigned)item_cats[nbase * CW + tid] : 0u;
+      }
       if (nbase < it1) {
         const int cnn = (int)min((long long)TK_CHUNK, it1 - nbase);
         const float* Yb = Y + nbase * (long long)F;
@@ -271,7 +324,15 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
       for (int g = 0; g < GRP; ++g) {
       const int c = c0 + g;
       const long long item = base + c;
-      const float s = g < gn ? sg[g] : -FLT_MAX;
+      float s = g < gn ? sg[g] : -FLT_MAX;
+      if constexpr (CW > 0) {
+        // one broadcast LDS read per word (c is wave-uniform)
+        unsigned hit = 0u;
+#pragma unroll
+        for (int w = 0; w < CW; ++w)
+          hit |= cats_lds[c * CW + w] & qc_lds[w * TK_UPB + lane];
+        s = hit != 0u ? s : -FLT_MAX;
+      }
       if (has_user && s > th) {
         if ((item_mask == nullptr || !item_mask[item]) &&
             (ban == nullptr ||
@@ -326,14 +387,24 @@ extern "C" void launch_topk_score(
     const long long* ban_indptr, const int* ban_indices,
     float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
-    unsigned long long* prof, hipStream_t stream)
+    unsigned long long* prof,
+    const int* item_cats, const int* query_cats, int cw,
+    hipStream_t stream)
 {
   dim3 grid(n_slices, (B + TK_UPB - 1) / TK_UPB);
   dim3 block(256);
+  /* category filter (cw > 0): PROF=false only; the binding rejects prof  */
+  /* together with cats                                                   */
+#define LAUNCH_CATS(FF, CWV)                                                \
+  hipLaunchKernelGGL((topk_score_kernel<FF, false, CWV>), grid, block,      \
+                     lds_bytes, stream, Xq, Y, item_mask, ban_indptr,       \
+                     ban_indices, out_val, out_idx, B, N, K, n_slices,      \
+                     item_base, nullptr, item_cats, query_cats)
 #define LAUNCH(FF)                                                          \
   do {                                                                      \
     size_t lds_bytes =                                                      \
         sizeof(float) * (TK_CHUNK * (FF + 4)) +                             \
+        sizeof(int) * (TK_CHUNK + TK_UPB) * cw +                            \
         (sizeof(float) + sizeof(int)) * TK_WAVES * TK_UPB * (K+1);        \
     /* small-K floor: the query-staging pass writes TK_UPB rows     */  \
     const size_t stage_need = sizeof(float) * TK_UPB * (FF + 4);        \
@@ -346,18 +417,30 @@ extern "C" void launch_topk_score(
       hipFuncSetAttribute(                                                  \
           reinterpret_cast<const void*>(&topk_score_kernel<FF, true>),      \
           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      attr_set_##FF = true;                                                 \
+      hipFuncSetAttribute(                                                  \
+          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 1>),  \
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
+      hipFuncSetAttribute(                                                  \
+          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 2>),  \
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
+      hipFuncSetAttribute(                                                  \
+          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 4>),  \
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
+      attr_set_##FF = true;                                             \
     }                                                                       \
-    if (prof != nullptr)                                                    \
+    if (cw == 1) LAUNCH_CATS(FF, 1);                                        \
+    else if (cw == 2) LAUNCH_CATS(FF, 2);                                   \
+    else if (cw == 4) LAUNCH_CATS(FF, 4);                                   \
+    else if (prof != nullptr)                                               \
       hipLaunchKernelGGL((topk_score_kernel<FF, true>), grid, block,        \
                          lds_bytes, stream, Xq, Y, item_mask, ban_indptr,   \
                          ban_indices, out_val, out_idx, B, N, K, n_slices,  \
-                         item_base, prof);                                  \
+                         item_base, prof, nullptr, nullptr);                \
     else                                                                    \
       hipLaunchKernelGGL((topk_score_kernel<FF, false>), grid, block,       \
                          lds_bytes, stream, Xq, Y, item_mask, ban_indptr,   \
                          ban_indices, out_val, out_idx, B, N, K, n_slices,  \
-                         item_base, nullptr);                               \
+                         item_base, nullptr, nullptr, nullptr);             \
   } while (0)
   switch (f) {
     case 16: LAUNCH(16); break;
@@ -367,4 +450,5 @@ extern "C" void launch_topk_score(
     default: break;
   }
 #undef LAUNCH
+#undef LAUNCH_CATS
 }

@@ -56,6 +56,9 @@
 #define TM_WAVES 4
 #define TM_QPW 16     // queries per wave
 #define TM_UPB (TM_WAVES * TM_QPW)  // queries per block
+// LDS row stride (words) of the staged category words, see cats_lds
+#define TM_CATS_STRIDE(CH, CW) \
+  ((CW) > 1 ? (CH) + 32 / ((CW) > 1 ? (CW) : 1) : (CH))
 
 typedef __attribute__((ext_vector_type(8))) unsigned short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -94,8 +97,22 @@ __device__ __forceinline__ bool tm_in_sorted(const int* arr, int n, int x) {
 // toward vmcnt and drains the staging pipeline every chunk), so QB=2
 // instantiations get min-waves 4 (128 VGPRs; LDS caps occupancy at
 // ~5 WGs/CU for K=20 anyway).
+//
+// CW = category words per item/query (0 = no category filter). With
+// CW > 0 item j is a candidate for query b iff
+//   OR_w (item_cats[j,w] & query_cats[b,w]) != 0.
+// The filter runs BEFORE the threshold test (scores of filtered items
+// become -FLT_MAX ahead of the max-reduce), not in the insert path where
+// item_mask/bans are checked: under a selective filter the K-th-best
+// threshold stays low relative to unfiltered scores, so an insert-time
+// filter would send almost every chunk into the serialized lane-group
+// slow path with a dependent global load per value. The chunk's CH x CW
+// words ride the same register-staged pipeline as the Y tile, into a
+// word-major [w][CH] LDS image (rows padded against write bank
+// conflicts) so a lane's four D rows are one b128.
+// Every CW > 0 line sits under `if constexpr`; CW == 0 is unchanged.
 template <int F, bool PROF, bool DBUF, int CH = TM_CHUNK,
-          int NWAVES = TM_WAVES, bool GLL = false, int QB = 1>
+          int NWAVES = TM_WAVES, bool GLL = false, int QB = 1, int CW = 0>
 __global__ __launch_bounds__(NWAVES * 64, QB == 1 ? 24 / NWAVES : 4)
 void topk_mfma_kernel(
     const unsigned short* __restrict__ Xq,   // B x F bf16
@@ -112,8 +129,15 @@ void topk_mfma_kernel(
     // K-th-best through L2, so each slice stops re-paying the full
     // insert ramp from -inf (insert volume was ~linear in n_slices)
     unsigned* __restrict__ th_g,
-    int kflags)  // bit 0: disable the ban bloom (A/B hook)
+    int kflags,  // bit 0: disable the ban bloom (A/B hook)
+    const int* __restrict__ item_cats,   // N x CW bit words (CW > 0)
+    const int* __restrict__ query_cats)  // B x CW accepted-bit words
 {
+  static_assert(CW == 0 || CW == 1 || CW == 2 || CW == 4,
+                "category words per item must be 1, 2 or 4");
+  static_assert(CW == 0 || (QB == 1 && !DBUF && !GLL && !PROF &&
+                            CH * CW <= NWAVES * 64),
+                "the category filter exists for the default variant only");
   constexpr int ROWB = F * 2;            // bytes per staged Y row
   constexpr int SWM = (F >= 64) ? 7 : 3; // XOR-swizzle row mask
   constexpr int KS = F / 32;             // MFMA K-steps per dot product
@@ -122,14 +146,25 @@ void topk_mfma_kernel(
   // DBUF: two ys buffers, ONE barrier per chunk (compute buf[i&1] while
   // draining the next chunk into buf[(i+1)&1])
   unsigned short* ys = reinterpret_cast<unsigned short*>(lds_raw);
-  float* topv = reinterpret_cast<float*>(
+  // category words of the staged chunk, word-major [CW][CSTR] (CW > 0).
+  // Row stride CSTR = CH + 32/CW words: the drain's transpose store has
+  // lanes t..t+CW-1 writing the CW words of one item, and with a stride
+  // of CH (a multiple of the 32 write banks) they collided CW ways; the
+  // pad spreads a half-wave's CW rows over disjoint bank ranges and keeps
+  // every row 16 B aligned for the epilogue's ds_read_b128.
+  constexpr int CSTR = TM_CATS_STRIDE(CH, CW);
+  unsigned* cats_lds = reinterpret_cast<unsigned*>(
       lds_raw + (DBUF ? 2 : 1) * CH * ROWB);
+  float* topv = reinterpret_cast<float*>(
+      lds_raw + (DBUF ? 2 : 1) * CH * ROWB + CW * CSTR * 4);
   const int KP = K + 1;  // stride coprime with the 32 banks (v3 lesson)
   constexpr int BS = NWAVES * 64;        // block size
   constexpr int UPB = NWAVES * TM_QPW;   // queries per query block
   constexpr int UPBT = UPB * QB;         // queries per workgroup
   int* topi = reinterpret_cast<int*>(topv + UPBT * KP);
   float* th_lds = reinterpret_cast<float*>(topi + UPBT * KP);
+  // per-query accepted-category words, word-major [CW][UPB] (CW > 0)
+  unsigned* qc_lds = reinterpret_cast<unsigned*>(th_lds + UPBT);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -207,6 +242,21 @@ void topk_mfma_kernel(
       }
     }
   }
+  // each query's accepted-category words, loaded once: word-major
+  // [CW][UPB] in LDS, not registers — under the 80-VGPR cap CW live
+  // registers per lane spilled the hot loop (F=64, CW=4: 444 B/lane of
+  // scratch against 196 B with the words in LDS). Queries past B hold
+  // zero, which filters everything.
+  if constexpr (CW > 0) {
+    if (lg == 0) {
+#pragma unroll
+      for (int w = 0; w < CW; ++w)
+        qc_lds[w * UPB + wave * TM_QPW + lq] = has_user[0]
+            ? (unsigned)query_cats[guser[0] * CW + w] : 0u;
+    }
+    // read back only by the writing wave's lanes, after the chunk
+    // loop's barriers
+  }
   if (probe) {
     const unsigned long long now = wall_clock64();
     acc_setup = now - pt;
@@ -228,7 +278,18 @@ void topk_mfma_kernel(
     grow[r] = lin / ROWB;
     goff[r] = grow[r] * F + (lin % ROWB) / 2;
   }
+  // category staging: the chunk's CH*CW words are contiguous in global
+  // memory (item-major), so thread t < CH*CW carries word t of the
+  // chunk — one coalesced dword per thread — and transposes it to the
+  // word-major LDS image on drain. Rows at or past it1 stage 0 =
+  // "filtered", which also covers the tail chunk.
+  unsigned cstg = 0u;
   auto load_stg = [&](long long cbase) {
+    if constexpr (CW > 0) {
+      if (tid < CH * CW)
+        cstg = (cbase + tid / CW < it1)
+            ? (unsigned)item_cats[cbase * CW + tid] : 0u;
+    }
     const unsigned short* yb_g = Y + cbase * F;
     const bool tail = cbase + CH > it1;
     if (!tail) {
@@ -251,6 +312,9 @@ void topk_mfma_kernel(
       const int col = lin % ROWB;
       const int dst = row * ROWB + (col ^ ((row & SWM) << 4));
       *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(yb) + dst) = stg[r];
+    }
+    if constexpr (CW > 0) {
+      if (tid < CH * CW) cats_lds[(tid % CW) * CSTR + tid / CW] = cstg;
     }
   };
   auto ybuf = [&](int i) -> unsigned short* {
@@ -358,6 +422,27 @@ void topk_mfma_kernel(
             row * ROWB + (col ^ ((row & SWM) << 4)));
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a, xf[qb][ks], acc[i], 0, 0, 0);
+      }
+    }
+
+    // ---- category filter, ahead of the threshold test: a filtered
+    // score becomes -FLT_MAX, which is never > th, so the max-reduce,
+    // the serialized insert, the cross-slice publish/fold and the
+    // write-out below need no change. One b128 per item fragment per
+    // word: the lane's D rows i*16 + lg*4 + r are contiguous in [w][CH].
+    if constexpr (CW > 0) {
+#pragma unroll
+      for (int i = 0; i < IFR; ++i) {
+        u32x4 hit = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int w = 0; w < CW; ++w) {
+          const u32x4 c = *reinterpret_cast<const u32x4*>(
+              &cats_lds[w * CSTR + i * 16 + lg * 4]);
+          hit |= c & qc_lds[w * UPB + wave * TM_QPW + lq];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          acc[i][r] = hit[r] != 0u ? acc[i][r] : -FLT_MAX;
       }
     }
 
@@ -499,7 +584,7 @@ static void launch_topk_mfma_wide(
         (topk_mfma_kernel<FF, false, false, TM_CHUNK, 8>), grid,
         dim3(512), lds_bytes, stream, Xq, Y, item_mask, ban_indptr,
         ban_indices, out_val, out_idx, B, N, K, n_slices, item_base,
-        nullptr, th_g, kflags);
+        nullptr, th_g, kflags, nullptr, nullptr);
   }
 }
 
@@ -508,10 +593,49 @@ extern "C" void launch_topk_mfma(
     const uint8_t* item_mask, const long long* ban_indptr,
     const int* ban_indices, float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
-    unsigned long long* prof, unsigned* th_g, hipStream_t stream)
+    unsigned long long* prof, unsigned* th_g,
+    const int* item_cats, const int* query_cats, int cw,
+    hipStream_t stream)
 {
   dim3 grid((B + TM_UPB - 1) / TM_UPB, n_slices);
   dim3 block(256);
+  if (cw > 0) {
+    // category filter: only the default variant (4 waves, TM_CHUNK, no
+    // DBUF/GLL/WIDE/QB2) exists with CW > 0, whatever the PIO_TOPK_*
+    // A/B hooks say; the binding rejects prof together with cats.
+    // Dynamic LDS grows by the chunk's category words and the queries'
+    // accepted words (at most 52 KB at F=128, K=64, CW=4 — under the
+    // 64 KB default limit).
+    const char* e_bl = getenv("PIO_TOPK_BLOOM");
+    const int kflags = (e_bl != nullptr && e_bl[0] == '0') ? 1 : 0;
+#define LAUNCH_C(FF, CWV)                                                    \
+  hipLaunchKernelGGL(                                                        \
+      (topk_mfma_kernel<FF, false, false, TM_CHUNK, TM_WAVES, false, 1,      \
+                        CWV>),                                               \
+      grid, block,                                                           \
+      (size_t)TM_CHUNK * (FF * 2) +                                          \
+          (size_t)CWV * TM_CATS_STRIDE(TM_CHUNK, CWV) * 4 +                  \
+          (sizeof(float) + sizeof(int)) * TM_UPB * (K + 1) +                 \
+          sizeof(float) * TM_UPB + sizeof(int) * TM_UPB * CWV,               \
+      stream, Xq, Y, item_mask, ban_indptr, ban_indices, out_val, out_idx,   \
+      B, N, K, n_slices, item_base, nullptr, th_g, kflags, item_cats,        \
+      query_cats)
+#define LAUNCH_CF(FF)                                                        \
+  do {                                                                       \
+    if (cw == 1) LAUNCH_C(FF, 1);                                            \
+    else if (cw == 2) LAUNCH_C(FF, 2);                                       \
+    else if (cw == 4) LAUNCH_C(FF, 4);                                       \
+  } while (0)
+    switch (f) {
+      case 32: LAUNCH_CF(32); break;
+      case 64: LAUNCH_CF(64); break;
+      case 128: LAUNCH_CF(128); break;
+      default: break;
+    }
+#undef LAUNCH_CF
+#undef LAUNCH_C
+    return;
+  }
   dim3 grid_w((B + 127) / 128, n_slices);
   const char* e_db = getenv("PIO_TOPK_DB");
   const bool use_db = e_db != nullptr && e_db[0] == '1';
@@ -561,30 +685,30 @@ extern "C" void launch_topk_mfma(
                               2>),                                           \
             grid_q2, block, lds_bytes, stream, Xq, Y, item_mask, ban_indptr, \
             ban_indices, out_val, out_idx, B, N, K, n_slices, item_base,     \
-            prof, th_g, kflags);                                                           \
+            prof, th_g, kflags, nullptr, nullptr);                                                           \
       else                                                                   \
         hipLaunchKernelGGL(                                                  \
             (topk_mfma_kernel<FF, false, false, TM_CHUNK, TM_WAVES, false,   \
                               2>),                                           \
             grid_q2, block, lds_bytes, stream, Xq, Y, item_mask, ban_indptr, \
             ban_indices, out_val, out_idx, B, N, K, n_slices, item_base,     \
-            nullptr, th_g, kflags);                                                        \
+            nullptr, th_g, kflags, nullptr, nullptr);                                                        \
     } else if (prof != nullptr) {                                            \
       if (use_db)                                                            \
         hipLaunchKernelGGL((topk_mfma_kernel<FF, true, true>), grid, block,  \
                            lds_bytes, stream, Xq, Y, item_mask, ban_indptr,  \
                            ban_indices, out_val, out_idx, B, N, K, n_slices, \
-                           item_base, prof, th_g, kflags);                                 \
+                           item_base, prof, th_g, kflags, nullptr, nullptr);                                 \
       else if (chunk == 128)                                                 \
         hipLaunchKernelGGL((topk_mfma_kernel<FF, true, false, 128>), grid,   \
                            block, lds_bytes, stream, Xq, Y, item_mask,       \
                            ban_indptr, ban_indices, out_val, out_idx, B, N,  \
-                           K, n_slices, item_base, prof, th_g, kflags);                    \
+                           K, n_slices, item_base, prof, th_g, kflags, nullptr, nullptr);                    \
       else                                                                   \
         hipLaunchKernelGGL((topk_mfma_kernel<FF, true, false>), grid, block, \
                            lds_bytes, stream, Xq, Y, item_mask, ban_indptr,  \
                            ban_indices, out_val, out_idx, B, N, K, n_slices, \
-                           item_base, prof, th_g, kflags);                                 \
+                           item_base, prof, th_g, kflags, nullptr, nullptr);                                 \
     } else if (use_wide) {                                                   \
       size_t lds_w = (size_t)TM_CHUNK * (FF * 2) +                           \
                      (sizeof(float) + sizeof(int)) * 128 * (K + 1) +         \
@@ -598,23 +722,23 @@ extern "C" void launch_topk_mfma(
         hipLaunchKernelGGL((topk_mfma_kernel<FF, false, true>), grid, block, \
                            lds_bytes, stream, Xq, Y, item_mask, ban_indptr,  \
                            ban_indices, out_val, out_idx, B, N, K, n_slices, \
-                           item_base, nullptr, th_g, kflags);                              \
+                           item_base, nullptr, th_g, kflags, nullptr, nullptr);                              \
       else if (chunk == 128)                                                 \
         hipLaunchKernelGGL((topk_mfma_kernel<FF, false, false, 128>), grid,  \
                            block, lds_bytes, stream, Xq, Y, item_mask,       \
                            ban_indptr, ban_indices, out_val, out_idx, B, N,  \
-                           K, n_slices, item_base, nullptr, th_g, kflags);                 \
+                           K, n_slices, item_base, nullptr, th_g, kflags, nullptr, nullptr);                 \
       else if (use_gll)                                                      \
         hipLaunchKernelGGL(                                                  \
             (topk_mfma_kernel<FF, false, false, TM_CHUNK, TM_WAVES, true>),  \
             grid, block, lds_bytes, stream, Xq, Y, item_mask, ban_indptr,    \
             ban_indices, out_val, out_idx, B, N, K, n_slices, item_base,     \
-            nullptr, th_g, kflags);                                                        \
+            nullptr, th_g, kflags, nullptr, nullptr);                                                        \
       else                                                                   \
         hipLaunchKernelGGL((topk_mfma_kernel<FF, false, false>), grid,       \
                            block, lds_bytes, stream, Xq, Y, item_mask,       \
                            ban_indptr, ban_indices, out_val, out_idx, B, N,  \
-                           K, n_slices, item_base, nullptr, th_g, kflags);                 \
+                           K, n_slices, item_base, nullptr, th_g, kflags, nullptr, nullptr);                 \
     }                                                                        \
   } while (0)
   switch (f) {

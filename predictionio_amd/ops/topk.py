@@ -51,12 +51,20 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                ban_indptr: Optional[torch.Tensor] = None,
                ban_indices: Optional[torch.Tensor] = None,
                n_slices: Optional[int] = None,
-               mode: Optional[str] = None
+               mode: Optional[str] = None,
+               item_cats: Optional[torch.Tensor] = None,
+               query_cats: Optional[torch.Tensor] = None
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K of (Xq @ Y.T) per query row, with optional global item mask
     (uint8, 1=banned) and per-query banned lists (CSR int32, sorted).
     Returns (values [B,K] fp32, indices [B,K] int64), sorted descending.
     Banned/empty slots carry -inf / -1.
+
+    item_cats [N,W] / query_cats [B,W] (int32 bit words, W in {1,2,4},
+    given together or not at all) add a per-query category filter: item
+    j is a candidate for query b iff any word of item_cats[j] &
+    query_cats[b] is non-zero. It composes with item_mask and the ban
+    lists — an item must pass all three.
 
     mode: "mfma" (default on GPU) scores on the matrix cores with bf16
     inputs / fp32 accumulate, then re-checks the surviving candidates
@@ -65,18 +73,20 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
+    _check_cats(item_cats, query_cats, B, N)
     if Xq.is_cuda:
         if K > 64:
             # the fused kernels keep K-entry per-query lists in LDS and
             # cap at 64; arbitrary `num` (the reference allows any) falls
             # back to a materialized masked matmul + torch.topk on device
             return _topk_torch_gpu(Xq, Y, K, item_mask, ban_indptr,
-                                   ban_indices)
+                                   ban_indices, item_cats, query_cats)
         if mode is None:
             mode = os.environ.get("PIO_TOPK_MODE", "mfma")
         if mode == "mfma" and _mfma_rank(f) is not None:
             return _topk_score_mfma(Xq, Y, K, item_mask, ban_indptr,
-                                    ban_indices, n_slices)
+                                    ban_indices, n_slices,
+                                    item_cats, query_cats)
         from predictionio_amd.ops import hip_ext
         pf = pad_rank(f)
         Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
@@ -92,7 +102,8 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
             Xp.contiguous(), Yp.contiguous(), K, int(n_slices),
             item_mask.contiguous() if item_mask is not None else None,
             ban_indptr.contiguous() if ban_indptr is not None else None,
-            ban_indices.contiguous() if ban_indices is not None else None, 0)
+            ban_indices.contiguous() if ban_indices is not None else None, 0,
+            item_cats=item_cats, query_cats=query_cats)
         # phase 2: merge per-slice candidates (small [B, n_slices*K] topk)
         mvals, pos = torch.topk(vals, K, dim=1)
         midx = torch.gather(idxs, 1, pos).long()
@@ -102,15 +113,53 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         midx[empty] = -1
         mvals = mvals.masked_fill(empty, float("-inf"))
         return mvals, midx
-    return topk_score_ref(Xq, Y, K, item_mask, ban_indptr, ban_indices)
+    return topk_score_ref(Xq, Y, K, item_mask, ban_indptr, ban_indices,
+                          item_cats, query_cats)
+
+
+def _check_cats(item_cats, query_cats, B: int, N: int) -> None:
+    """The category-filter contract (the native binding re-validates
+    it): both or neither, int32, contiguous, [N,W] / [B,W], W in
+    {1,2,4}. A mismatch raises — there is no fallback."""
+    if (item_cats is None) != (query_cats is None):
+        raise ValueError("item_cats and query_cats must be given together")
+    if item_cats is None:
+        return
+    for name, t, rows in (("item_cats", item_cats, N),
+                          ("query_cats", query_cats, B)):
+        if t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 2-D int32 tensor")
+        if t.shape[0] != rows:
+            raise ValueError(f"{name} must have {rows} rows, "
+                             f"got {t.shape[0]}")
+    W = item_cats.shape[1]
+    if W not in (1, 2, 4) or query_cats.shape[1] != W:
+        raise ValueError("category words W must be 1, 2 or 4 and equal "
+                         "for item_cats and query_cats")
+
+
+def _cats_miss(item_cats: torch.Tensor, query_cats: torch.Tensor
+               ) -> torch.Tensor:
+    """[B,N] bool, True where item j fails query b's category filter
+    (word by word, so no B x N x W intermediate)."""
+    hit = None
+    for w in range(item_cats.shape[1]):
+        h = (item_cats[:, w].unsqueeze(0)
+             & query_cats[:, w].unsqueeze(1)) != 0
+        hit = h if hit is None else (hit | h)
+    return ~hit
 
 
 def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
-                    item_mask, ban_indptr, ban_indices
+                    item_mask, ban_indptr, ban_indices,
+                    item_cats=None, query_cats=None
                     ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Device fallback for K > 64: materialized masked score matrix +
     torch.topk. Memory: B x N fp32 — callers with huge B should batch."""
     scores = Xq @ Y.t()
+    if item_cats is not None:
+        scores = scores.masked_fill(_cats_miss(item_cats, query_cats),
+                                    float("-inf"))
     if item_mask is not None:
         scores = scores.masked_fill(item_mask.bool().unsqueeze(0),
                                     float("-inf"))
@@ -137,7 +186,8 @@ def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
 
 def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                      item_mask, ban_indptr, ban_indices,
-                     n_slices: Optional[int]
+                     n_slices: Optional[int],
+                     item_cats=None, query_cats=None
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     """MFMA path: bf16 matrix-core scoring selects ~2K candidates per
     query (masks/bans applied in-kernel), then the candidates are
@@ -158,9 +208,16 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         # per-query top-K lists), so the target shrinks for large K —
         # a 1536-WG grid at K=64 only fits 768 at a time and the
         # second pass doubled the time (profiles/serve_k_sweep_r2.log)
-        upw = 128 if os.environ.get("PIO_TOPK_QB") == "2" else 64
+        # (the category path always runs the default 64-query variant)
+        upw = 128 if (os.environ.get("PIO_TOPK_QB") == "2"
+                      and item_cats is None) else 64
         ublocks = (B + upw - 1) // upw
         lds = 64 * 2 * pf + 8 * (upw // 64) * 64 * (K + 1) + 4 * 64
+        if item_cats is not None:
+            # staged item category words (rows padded by 32/W words
+            # for W > 1) + the queries' accepted words
+            W = item_cats.shape[1]
+            lds += W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
         target = 256 * max(1, min(6, (160 * 1024) // lds))
         n_slices = max(2, min(target // ublocks, (N + 255) // 256))
     # Y's bf16 copy is cached (factors are static across serving batches);
@@ -171,7 +228,8 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         int(n_slices),
         item_mask.contiguous() if item_mask is not None else None,
         ban_indptr.contiguous() if ban_indptr is not None else None,
-        ban_indices.contiguous() if ban_indices is not None else None, 0)
+        ban_indices.contiguous() if ban_indices is not None else None, 0,
+        item_cats=item_cats, query_cats=query_cats)
     # merge candidate groups down to a 2K shortlist on the bf16 scores
     C = min(vals.shape[1], 2 * K)
     cv, pos = torch.topk(vals, C, dim=1)
@@ -194,9 +252,14 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
 
 
 def topk_score_ref(Xq, Y, K, item_mask=None, ban_indptr=None,
-                   ban_indices=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   ban_indices=None, item_cats=None, query_cats=None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch reference (CPU path + GPU numerics baseline)."""
+    _check_cats(item_cats, query_cats, Xq.shape[0], Y.shape[0])
     scores = Xq.float() @ Y.float().t()  # B x N
+    if item_cats is not None:
+        scores = scores.masked_fill(_cats_miss(item_cats, query_cats),
+                                    float("-inf"))
     if item_mask is not None:
         scores = scores.masked_fill(item_mask.bool().unsqueeze(0),
                                     float("-inf"))

@@ -22,18 +22,24 @@ def sharded_topk_score(Xq: torch.Tensor, Y_local: torch.Tensor, K: int,
                        item_base: int,
                        item_mask: Optional[torch.Tensor] = None,
                        ban_indptr: Optional[torch.Tensor] = None,
-                       ban_indices: Optional[torch.Tensor] = None
+                       ban_indices: Optional[torch.Tensor] = None,
+                       item_cats: Optional[torch.Tensor] = None,
+                       query_cats: Optional[torch.Tensor] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K over the UNION of all ranks' item shards.
 
     Xq is replicated (every rank scores the same query batch); Y_local is
     this rank's item rows, whose global ids start at `item_base`. Ban
-    lists are in LOCAL shard coordinates. Returns (values, global indices)
-    identical on every rank.
+    lists are in LOCAL shard coordinates. The optional category filter
+    follows the same split: `item_cats` is row-sharded like `Y_local`,
+    `query_cats` is replicated like `Xq`. Returns (values, global
+    indices) identical on every rank.
     """
     v, idx = topk_ops.topk_score(Xq, Y_local, K, item_mask=item_mask,
                                  ban_indptr=ban_indptr,
-                                 ban_indices=ban_indices)
+                                 ban_indices=ban_indices,
+                                 item_cats=item_cats,
+                                 query_cats=query_cats)
     gidx = torch.where(idx >= 0, idx + item_base, idx)
     if not pdist.is_distributed():
         return v, gidx

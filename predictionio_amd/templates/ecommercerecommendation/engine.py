@@ -177,7 +177,11 @@ class ECommModel:
                  item_factors: torch.Tensor, item_factors_norm: torch.Tensor,
                  user_map: BiMap, item_map: BiMap,
                  items: Dict[str, Item], popular_count: Dict[int, int],
-                 category_masks=None):
+                 category_masks=None, category_bits=None,
+                 category_bits_built: bool = False):
+        """category_bits_built=True says `category_bits` is the outcome
+        of CategoryBits.build, so None means "too many categories";
+        otherwise a missing value is built on first use."""
         self.rank = rank
         self.user_features = user_features
         self.item_factors = item_factors
@@ -188,6 +192,28 @@ class ECommModel:
         self.popular_count = popular_count
         self.item_inv = item_map.inverse_array()
         self.category_masks = category_masks
+        self.category_bits = category_bits
+        self._cat_bits_built = (category_bits_built
+                                or category_bits is not None)
+
+    def cat_bits(self):
+        """Category bit words for the fused per-query filter (train-time;
+        lazily rebuilt for models persisted before they existed). None
+        when the catalog has too many categories for the bit words."""
+        if not getattr(self, "_cat_bits_built", False):
+            from predictionio_amd.templates.common import CategoryBits
+            self.category_bits = CategoryBits.build(
+                self.items, self.item_map, self.item_factors.device)
+            self._cat_bits_built = True
+        return self.category_bits
+
+    def item_inv_np(self):
+        """item index -> external id as a numpy array (vectorized
+        fancy-indexing for the batch-predict epilogue)."""
+        if getattr(self, "_item_inv_np", None) is None:
+            import numpy as np
+            self._item_inv_np = np.asarray(self.item_inv, dtype=object)
+        return self._item_inv_np
 
     def cat_masks(self):
         """Device category masks (train-time; lazily rebuilt for models
@@ -277,37 +303,50 @@ class ECommAlgorithm(Algorithm):
             for e in pd.buy_events:
                 pop[item_map[e.item]] += 1
         Yn = torch.nn.functional.normalize(Y, dim=1, eps=1e-9)
-        from predictionio_amd.templates.common import CategoryMasks
+        from predictionio_amd.templates.common import (
+            CategoryBits, CategoryMasks,
+        )
         cm = CategoryMasks.build(pd.items, item_map, Y.device)
+        cb = CategoryBits.build(pd.items, item_map, Y.device)
         return ECommModel(p.rank, X, Y, Yn, user_map, item_map, pd.items,
-                          dict(pop), cm)
+                          dict(pop), cm, cb, category_bits_built=True)
 
     # ------------------------------------------------------------ filters
 
     def _gen_black_list(self, q: Query) -> Set[str]:
         """Query blacklist + seen events + unavailable items, each live
         lookup bounded by 200 ms (genBlackList :330-398)."""
-        black: Set[str] = set(q.black_list or [])
-        if self.params.get("unseenOnly", False):
-            seen_events = self.params.get("seenEvents", ["view", "buy"])
-            try:
-                seen = event_store.find_by_entity(
-                    app_name=self.params["appName"], entity_type="user",
-                    entity_id=q.user, event_names=seen_events,
-                    target_entity_type="item", timeout=0.2)
-                black |= {e.target_entity_id for e in seen}
-            except TimeoutError:
-                pass  # degrade: no seen filter (reference logs + continues)
+        return (set(q.black_list or []) | self._seen_items(q)
+                | self._unavailable_items())
+
+    def _seen_items(self, q: Query) -> Set[str]:
+        """The user's seen items when unseenOnly is set (one live lookup,
+        200 ms, degrading to empty)."""
+        if not self.params.get("unseenOnly", False):
+            return set()
+        seen_events = self.params.get("seenEvents", ["view", "buy"])
+        try:
+            seen = event_store.find_by_entity(
+                app_name=self.params["appName"], entity_type="user",
+                entity_id=q.user, event_names=seen_events,
+                target_entity_type="item", timeout=0.2)
+            return {e.target_entity_id for e in seen}
+        except TimeoutError:
+            return set()  # degrade: no seen filter (reference logs on)
+
+    def _unavailable_items(self) -> Set[str]:
+        """The latest `$set constraint unavailableItems` (one live lookup,
+        200 ms, degrading to empty)."""
         try:
             constr = event_store.find_by_entity(
                 app_name=self.params["appName"], entity_type="constraint",
                 entity_id="unavailableItems", event_names=["$set"],
                 limit=1, latest=True, timeout=0.2)
             if constr:
-                black |= set(constr[0].properties.get("items") or [])
+                return set(constr[0].properties.get("items") or [])
         except TimeoutError:
             pass
-        return black
+        return set()
 
     def _mask(self, model: ECommModel, q: Query, black: Set[str]
               ) -> torch.Tensor:
@@ -396,6 +435,98 @@ class ECommAlgorithm(Algorithm):
             else:
                 scores = self._predict_default(model, mask, q)
         return PredictedResult(self._apply_weights(model, scores)[:q.num])
+
+    def batch_predict(self, model: ECommModel, queries):
+        """Device-batched predict: at most two fused top-K launches for
+        the whole batch (known users over item_factors, cold users with
+        recent views over item_factors_norm). Per query, `categories`
+        becomes a row of category bit words and blackList + seen items a
+        sorted ban list in one CSR; the unavailableItems constraint is
+        fetched once per batch and becomes the shared item_mask. Live
+        per-user lookups stay per query. Queries with a whiteList (rare,
+        and a batch-wide mask does not fit them) and models without
+        category bits go through predict() one by one."""
+        qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
+              for i, q in queries]
+        bits = model.cat_bits()
+        out: Dict[int, PredictedResult] = {}
+        if bits is None:
+            return [(i, self.predict(model, q)) for i, q in qs]
+        batch = []
+        for i, q in qs:
+            if q.white_list is not None:
+                out[i] = self.predict(model, q)
+            else:
+                batch.append((i, q))
+        if batch:
+            dev = model.item_factors.device
+            n = len(model.item_map)
+            unavailable = self._unavailable_items()
+            item_mask = None
+            un_idx = [model.item_map[x] for x in unavailable
+                      if x in model.item_map]
+            if un_idx:
+                item_mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+                item_mask[torch.tensor(un_idx, device=dev)] = 1
+            known, cold = [], []  # (i, q, ban list, user row | recent rows)
+            for i, q in batch:
+                black = set(q.black_list or []) | self._seen_items(q)
+                ban = sorted({model.item_map[x] for x in black
+                              if x in model.item_map})
+                uidx = model.user_map.get(q.user)
+                if uidx is not None and uidx < model.user_features.shape[0]:
+                    known.append((i, q, ban, uidx))
+                    continue
+                recent = [model.item_map[x] for x in self._recent_items(q)
+                          if x in model.item_map]
+                if recent:
+                    cold.append((i, q, ban, recent))
+                else:
+                    out[i] = PredictedResult(self._apply_weights(
+                        model, self._predict_default(
+                            model, self._mask(model, q, black | unavailable),
+                            q))[:q.num])
+            if known:
+                Xq = model.user_features[
+                    torch.tensor([g[3] for g in known], device=dev)]
+                self._batch_topk(model, bits, known, Xq,
+                                 model.item_factors, item_mask, out)
+            if cold:
+                rows = torch.tensor([r for g in cold for r in g[3]],
+                                    device=dev)
+                seg = torch.tensor(
+                    [k for k, g in enumerate(cold) for _ in g[3]],
+                    device=dev)
+                Yn = model.item_factors_norm
+                Xq = torch.zeros((len(cold), Yn.shape[1]), dtype=Yn.dtype,
+                                 device=dev).index_add_(0, seg, Yn[rows])
+                self._batch_topk(model, bits, cold, Xq, Yn, item_mask, out)
+        return [(i, out[i]) for i, _ in qs]
+
+    def _batch_topk(self, model, bits, group, Xq, Y, item_mask, out):
+        """One fused launch for `group` [(i, q, ban list, _)]; K is the
+        group's largest num and every result is cut to its own."""
+        import numpy as np
+        from predictionio_amd.templates.common import ban_csr
+        dev = Y.device
+        ban_indptr, ban_indices = ban_csr([g[2] for g in group], dev)
+        query_cats = torch.from_numpy(np.stack(
+            [bits.query_words(g[1].categories) for g in group])).to(dev)
+        num = max(g[1].num for g in group)
+        v, ix = topk_ops.topk_score(
+            Xq, Y, num, item_mask=item_mask, ban_indptr=ban_indptr,
+            ban_indices=ban_indices, item_cats=bits.item_words,
+            query_cats=query_cats)
+        v_np = v.cpu().numpy()
+        ix_np = ix.cpu().numpy()
+        names = model.item_inv_np()[np.clip(ix_np, 0, None)]
+        for r, g in enumerate(group):
+            i, q = g[0], g[1]
+            scores = [ItemScore(nm, float(s)) for nm, s, it in
+                      zip(names[r, :q.num], v_np[r, :q.num],
+                          ix_np[r, :q.num]) if it >= 0]
+            out[i] = PredictedResult(
+                self._apply_weights(model, scores)[:q.num])
 
     def _predict_default(self, model: ECommModel, mask, q: Query
                          ) -> List[ItemScore]:

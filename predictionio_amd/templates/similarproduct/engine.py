@@ -135,12 +135,38 @@ class SimilarModel:
     """Normalized item factors + maps + categories (P2L local model)."""
 
     def __init__(self, item_factors_norm: torch.Tensor, item_map: BiMap,
-                 items: Dict[str, Item], category_masks=None):
+                 items: Dict[str, Item], category_masks=None,
+                 category_bits=None, category_bits_built: bool = False):
+        """category_bits_built=True says `category_bits` is the outcome
+        of CategoryBits.build, so None means "too many categories";
+        otherwise a missing value is built on first use."""
         self.item_factors_norm = item_factors_norm  # L2-normalized rows
         self.item_map = item_map
         self.items = items
         self.item_inv = item_map.inverse_array()
         self.category_masks = category_masks
+        self.category_bits = category_bits
+        self._cat_bits_built = (category_bits_built
+                                or category_bits is not None)
+
+    def cat_bits(self):
+        """Category bit words for the fused per-query filter (train-time;
+        lazily rebuilt for models persisted before they existed). None
+        when the catalog has too many categories for the bit words."""
+        if not getattr(self, "_cat_bits_built", False):
+            from predictionio_amd.templates.common import CategoryBits
+            self.category_bits = CategoryBits.build(
+                self.items, self.item_map, self.item_factors_norm.device)
+            self._cat_bits_built = True
+        return self.category_bits
+
+    def item_inv_np(self):
+        """item index -> external id as a numpy array (vectorized
+        fancy-indexing for the batch-predict epilogue)."""
+        if getattr(self, "_item_inv_np", None) is None:
+            import numpy as np
+            self._item_inv_np = np.asarray(self.item_inv, dtype=object)
+        return self._item_inv_np
 
     def cat_masks(self):
         """Device category masks (built at train time; lazily rebuilt
@@ -183,9 +209,13 @@ class ALSAlgorithm(Algorithm):
         _, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)
         Yn = torch.nn.functional.normalize(Y, dim=1, eps=1e-9)
-        from predictionio_amd.templates.common import CategoryMasks
+        from predictionio_amd.templates.common import (
+            CategoryBits, CategoryMasks,
+        )
         cm = CategoryMasks.build(pd.items, item_map, Yn.device)
-        return SimilarModel(Yn, item_map, pd.items, cm)
+        cb = CategoryBits.build(pd.items, item_map, Yn.device)
+        return SimilarModel(Yn, item_map, pd.items, cm, cb,
+                            category_bits_built=True)
 
     def _masks(self, model: SimilarModel, q: Query,
                dev) -> Optional[torch.Tensor]:
@@ -229,6 +259,69 @@ class ALSAlgorithm(Algorithm):
         return PredictedResult([
             ItemScore(model.item_inv[int(i)], float(s))
             for s, i in zip(v, idx) if i >= 0])
+
+    def batch_predict(self, model: SimilarModel, queries):
+        """Device-batched predict: ONE fused top-K launch over
+        item_factors_norm for the whole batch. Per query, `categories`
+        becomes a row of category bit words, and blackList + the query's
+        own items a sorted ban list in one CSR. Queries with no known
+        item give an empty result; queries with a whiteList (rare, and a
+        batch-wide mask does not fit them) and models without category
+        bits go through predict() one by one."""
+        import numpy as np
+        from predictionio_amd.templates.common import ban_csr
+        qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
+              for i, q in queries]
+        bits = model.cat_bits()
+        # the per-query fallback is THIS class's predict on the parsed
+        # Query — a subclass (RecommendedUserAlgorithm) overrides predict
+        # for its own query type and hands batch_predict ready Queries
+        if bits is None:
+            return [(i, ALSAlgorithm.predict(self, model, q))
+                    for i, q in qs]
+        out: Dict[int, PredictedResult] = {}
+        group = []  # (i, q, query item rows)
+        for i, q in qs:
+            if q.white_list is not None:
+                out[i] = ALSAlgorithm.predict(self, model, q)
+                continue
+            rows = [model.item_map[x] for x in q.items
+                    if x in model.item_map]
+            if rows:
+                group.append((i, q, rows))
+            else:
+                out[i] = PredictedResult([])
+        if group:
+            Yn = model.item_factors_norm
+            dev = Yn.device
+            # sum of cosines = (sum of normalized query vectors) . Yn
+            rows = torch.tensor([r for g in group for r in g[2]],
+                                device=dev)
+            seg = torch.tensor(
+                [k for k, g in enumerate(group) for _ in g[2]], device=dev)
+            Xq = torch.zeros((len(group), Yn.shape[1]), dtype=Yn.dtype,
+                             device=dev).index_add_(0, seg, Yn[rows])
+            # the query's own items are never returned
+            ban_indptr, ban_indices = ban_csr(
+                [sorted(set(g[2]) | {model.item_map[x]
+                                     for x in (g[1].black_list or [])
+                                     if x in model.item_map})
+                 for g in group], dev)
+            query_cats = torch.from_numpy(np.stack(
+                [bits.query_words(g[1].categories) for g in group])).to(dev)
+            num = max(g[1].num for g in group)
+            v, ix = topk_ops.topk_score(
+                Xq, Yn, num, ban_indptr=ban_indptr, ban_indices=ban_indices,
+                item_cats=bits.item_words, query_cats=query_cats)
+            v_np = v.cpu().numpy()
+            ix_np = ix.cpu().numpy()
+            names = model.item_inv_np()[np.clip(ix_np, 0, None)]
+            for r, (i, q, _) in enumerate(group):
+                out[i] = PredictedResult(
+                    [ItemScore(nm, float(s)) for nm, s, it in
+                     zip(names[r, :q.num], v_np[r, :q.num],
+                         ix_np[r, :q.num]) if it >= 0])
+        return [(i, out[i]) for i, _ in qs]
 
 
 class CooccurrenceModel:
@@ -393,6 +486,15 @@ class RecommendedUserAlgorithm(ALSAlgorithm):
         return super().predict(
             model, Query(items=q.users, num=q.num,
                          white_list=q.white_list, black_list=q.black_list))
+
+    def batch_predict(self, model: SimilarModel, queries):
+        return super().batch_predict(
+            model,
+            [(i, Query(items=q.users, num=q.num, white_list=q.white_list,
+                       black_list=q.black_list))
+             for i, q in ((i, q if isinstance(q, UserQuery)
+                           else UserQuery.from_json(q))
+                          for i, q in queries)])
 
 
 class RecommendedUserEngine(EngineFactory):
