@@ -22,7 +22,7 @@ Registry config:
 from __future__ import annotations
 
 import base64
-from datetime import datetime, timezone
+from datetime import datetime, timedelta, timezone
 from typing import Any, Dict, Iterable, List, Optional, Sequence
 
 from predictionio_amd.data.events import DataMap, Event, PropertyMap
@@ -35,8 +35,16 @@ from predictionio_amd.data.storage.base import (
 # ------------------------------------------------------------- marshalling
 
 
+_EPOCH = datetime(1970, 1, 1, tzinfo=timezone.utc)
+
+
 def ms(dt: Optional[datetime]) -> Optional[int]:
-    return None if dt is None else int(dt.timestamp() * 1000)
+    """Whole epoch milliseconds, in integer arithmetic: the float form
+    int(dt.timestamp() * 1000) lost a millisecond whenever the product
+    landed just under an integer (…155 ms -> …154.9995)."""
+    if dt is None:
+        return None
+    return (dt.astimezone(timezone.utc) - _EPOCH) // timedelta(milliseconds=1)
 
 
 def from_ms(v) -> Optional[datetime]:

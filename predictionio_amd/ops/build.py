@@ -17,6 +17,7 @@ CSRC = os.path.join(OPS_DIR, "csrc")
 SO_PATH = os.path.join(OPS_DIR, "_pio_hip.so")
 SOURCES = ["bindings.cpp", "als_kernels.hip", "topk_kernels.hip",
            "topk_mfma.hip"]
+HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
@@ -37,7 +38,7 @@ def needs_build() -> bool:
     if not os.path.exists(SO_PATH):
         return True
     so_mtime = os.path.getmtime(SO_PATH)
-    for s in SOURCES:
+    for s in SOURCES + HEADERS:
         if os.path.getmtime(os.path.join(CSRC, s)) > so_mtime:
             return True
     return False

@@ -74,6 +74,61 @@ int check_cats(const c10::optional<torch::Tensor>& item_cats,
   return (int)W;
 }
 
+// The arguments topk_score and topk_score_mfma share, validated against
+// the batch B and item count N and reduced to the raw pointers the
+// launchers take (nullptr = not given; cw = 0 = no category filter).
+struct TopkArgs {
+  const uint8_t* mask = nullptr;
+  const long long* ban_indptr = nullptr;
+  const int* ban_indices = nullptr;
+  unsigned long long* prof = nullptr;
+  const int* item_cats = nullptr;
+  const int* query_cats = nullptr;
+  int cw = 0;
+};
+
+TopkArgs check_topk_args(const c10::optional<torch::Tensor>& item_mask,
+                         const c10::optional<torch::Tensor>& ban_indptr,
+                         const c10::optional<torch::Tensor>& ban_indices,
+                         const c10::optional<torch::Tensor>& prof,
+                         const c10::optional<torch::Tensor>& item_cats,
+                         const c10::optional<torch::Tensor>& query_cats,
+                         int64_t B, int64_t N) {
+  TopkArgs a;
+  a.cw = check_cats(item_cats, query_cats, B, N, prof.has_value());
+  if (a.cw) {
+    a.item_cats = item_cats->data_ptr<int>();
+    a.query_cats = query_cats->data_ptr<int>();
+  }
+  if (item_mask.has_value()) {
+    TORCH_CHECK(item_mask->is_cuda() && item_mask->is_contiguous() &&
+                    item_mask->scalar_type() == torch::kUInt8,
+                "item_mask must be contiguous u8 GPU");
+    TORCH_CHECK(item_mask->size(0) == N, "item_mask size mismatch");
+    a.mask = item_mask->data_ptr<uint8_t>();
+  }
+  if (ban_indptr.has_value()) {
+    TORCH_CHECK(ban_indices.has_value(), "ban_indices required with ban_indptr");
+    TORCH_CHECK(ban_indptr->is_cuda() && ban_indptr->is_contiguous() &&
+                ban_indptr->scalar_type() == torch::kInt64);
+    TORCH_CHECK(ban_indices->is_cuda() && ban_indices->is_contiguous() &&
+                ban_indices->scalar_type() == torch::kInt32);
+    TORCH_CHECK(ban_indptr->size(0) == B + 1, "ban_indptr must be B+1");
+    a.ban_indptr = reinterpret_cast<const long long*>(
+        ban_indptr->data_ptr<int64_t>());
+    a.ban_indices = ban_indices->data_ptr<int>();
+  }
+  if (prof.has_value()) {
+    TORCH_CHECK(prof->is_cuda() && prof->is_contiguous() &&
+                    prof->scalar_type() == torch::kUInt64 &&
+                    prof->numel() >= 5,
+                "prof must be a contiguous u64[5] GPU tensor");
+    a.prof = reinterpret_cast<unsigned long long*>(
+        prof->data_ptr<uint64_t>());
+  }
+  return a;
+}
+
 // Solve one ALS half-iteration: for every CSR row r,
 //   explicit: (sum_i y_i y_i^T + lambda*nnz_r*I) x_r = sum_i r_i y_i
 //   implicit: (YtY + sum_i alpha*r * y_i y_i^T + lambda*I) x_r
@@ -153,7 +208,7 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
 }
 
 // Fused masked top-K scoring: per-slice candidate groups; caller merges
-// with a small torch.topk. Returns (vals [B, n_slices*K], idx i32).
+// with a small torch.topk. Returns (vals [B, n_slices*4*K], idx i32).
 std::tuple<torch::Tensor, torch::Tensor> topk_score(
     torch::Tensor Xq, torch::Tensor Y, int64_t K, int64_t n_slices,
     c10::optional<torch::Tensor> item_mask,
@@ -171,56 +226,27 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   TORCH_CHECK(n_slices >= 1);
-  const int cw = check_cats(item_cats, query_cats, B, N, prof.has_value());
-  const int* ic_ptr = cw ? item_cats->data_ptr<int>() : nullptr;
-  const int* qc_ptr = cw ? query_cats->data_ptr<int>() : nullptr;
-  const uint8_t* mask_ptr = nullptr;
-  if (item_mask.has_value()) {
-    TORCH_CHECK(item_mask->is_cuda() && item_mask->is_contiguous() &&
-                    item_mask->scalar_type() == torch::kUInt8,
-                "item_mask must be contiguous u8 GPU");
-    TORCH_CHECK(item_mask->size(0) == N, "item_mask size mismatch");
-    mask_ptr = item_mask->data_ptr<uint8_t>();
-  }
-  const long long* bi_ptr = nullptr;
-  const int* bx_ptr = nullptr;
-  if (ban_indptr.has_value()) {
-    TORCH_CHECK(ban_indices.has_value(), "ban_indices required with ban_indptr");
-    TORCH_CHECK(ban_indptr->is_cuda() && ban_indptr->is_contiguous() &&
-                ban_indptr->scalar_type() == torch::kInt64);
-    TORCH_CHECK(ban_indices->is_cuda() && ban_indices->is_contiguous() &&
-                ban_indices->scalar_type() == torch::kInt32);
-    TORCH_CHECK(ban_indptr->size(0) == B + 1, "ban_indptr must be B+1");
-    bi_ptr = reinterpret_cast<const long long*>(ban_indptr->data_ptr<int64_t>());
-    bx_ptr = ban_indices->data_ptr<int>();
-  }
+  const TopkArgs a = check_topk_args(item_mask, ban_indptr, ban_indices, prof,
+                                     item_cats, query_cats, B, N);
   // the kernel emits TK_WAVES=4 independent candidate groups per slice
   auto out_val = torch::empty({B, n_slices * 4 * K}, Xq.options());
   auto out_idx = torch::empty({B, n_slices * 4 * K},
                               Xq.options().dtype(torch::kInt32));
-  unsigned long long* prof_ptr = nullptr;
-  if (prof.has_value()) {
-    TORCH_CHECK(prof->is_cuda() && prof->is_contiguous() &&
-                    prof->scalar_type() == torch::kUInt64 &&
-                    prof->numel() >= 5,
-                "prof must be a contiguous u64[5] GPU tensor");
-    prof_ptr = reinterpret_cast<unsigned long long*>(
-        prof->data_ptr<uint64_t>());
-  }
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
   hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  launch_topk_score(Xq.data_ptr<float>(), Y.data_ptr<float>(), mask_ptr,
-                    bi_ptr, bx_ptr, out_val.data_ptr<float>(),
+  launch_topk_score(Xq.data_ptr<float>(), Y.data_ptr<float>(), a.mask,
+                    a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
                     out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f,
-                    (int)K, (int)n_slices, (int)item_base, prof_ptr, ic_ptr,
-                    qc_ptr, cw, stream);
+                    (int)K, (int)n_slices, (int)item_base, a.prof,
+                    a.item_cats, a.query_cats, a.cw, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }
 
 // MFMA variant of topk_score: bf16 query/item factors (fp32 accumulate on
-// the matrix cores). Same output layout as topk_score — candidate groups
-// (n_slices*4) per query; the Python wrapper merges and fp32-rescores.
+// the matrix cores). Output is n_slices candidate groups of K per query
+// (topk_score emits n_slices*4); the Python wrapper merges and
+// fp32-rescores.
 std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
     torch::Tensor Xq, torch::Tensor Y, int64_t K, int64_t n_slices,
     c10::optional<torch::Tensor> item_mask,
@@ -243,45 +269,14 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   TORCH_CHECK(n_slices >= 1);
-  const int cw = check_cats(item_cats, query_cats, B, N, prof.has_value());
-  const int* ic_ptr = cw ? item_cats->data_ptr<int>() : nullptr;
-  const int* qc_ptr = cw ? query_cats->data_ptr<int>() : nullptr;
-  const uint8_t* mask_ptr = nullptr;
-  if (item_mask.has_value()) {
-    TORCH_CHECK(item_mask->is_cuda() && item_mask->is_contiguous() &&
-                    item_mask->scalar_type() == torch::kUInt8,
-                "item_mask must be contiguous u8 GPU");
-    TORCH_CHECK(item_mask->size(0) == N, "item_mask size mismatch");
-    mask_ptr = item_mask->data_ptr<uint8_t>();
-  }
-  const long long* bi_ptr = nullptr;
-  const int* bx_ptr = nullptr;
-  if (ban_indptr.has_value()) {
-    TORCH_CHECK(ban_indices.has_value(), "ban_indices required");
-    TORCH_CHECK(ban_indptr->is_cuda() && ban_indptr->is_contiguous() &&
-                ban_indptr->scalar_type() == torch::kInt64);
-    TORCH_CHECK(ban_indices->is_cuda() && ban_indices->is_contiguous() &&
-                ban_indices->scalar_type() == torch::kInt32);
-    TORCH_CHECK(ban_indptr->size(0) == B + 1, "ban_indptr must be B+1");
-    bi_ptr = reinterpret_cast<const long long*>(
-        ban_indptr->data_ptr<int64_t>());
-    bx_ptr = ban_indices->data_ptr<int>();
-  }
+  const TopkArgs a = check_topk_args(item_mask, ban_indptr, ban_indices, prof,
+                                     item_cats, query_cats, B, N);
   // one candidate group per slice per query (the kernel keeps a single
   // shared top-K list per query per workgroup)
   auto out_val = torch::empty({B, n_slices * K},
                               Xq.options().dtype(torch::kFloat32));
   auto out_idx = torch::empty({B, n_slices * K},
                               Xq.options().dtype(torch::kInt32));
-  unsigned long long* prof_ptr = nullptr;
-  if (prof.has_value()) {
-    TORCH_CHECK(prof->is_cuda() && prof->is_contiguous() &&
-                    prof->scalar_type() == torch::kUInt64 &&
-                    prof->numel() >= 5,
-                "prof must be a contiguous u64[5] GPU tensor");
-    prof_ptr = reinterpret_cast<unsigned long long*>(
-        prof->data_ptr<uint64_t>());
-  }
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
   hipStream_t stream =
       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
@@ -302,10 +297,11 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   }
   launch_topk_mfma(
       reinterpret_cast<const unsigned short*>(Xq.data_ptr()),
-      reinterpret_cast<const unsigned short*>(Y.data_ptr()), mask_ptr,
-      bi_ptr, bx_ptr, out_val.data_ptr<float>(), out_idx.data_ptr<int>(),
-      (int)B, (long long)N, (int)f, (int)K, (int)n_slices, (int)item_base,
-      prof_ptr, th_g_ptr, ic_ptr, qc_ptr, cw, stream);
+      reinterpret_cast<const unsigned short*>(Y.data_ptr()), a.mask,
+      a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
+      out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f, (int)K,
+      (int)n_slices, (int)item_base, a.prof, th_g_ptr, a.item_cats,
+      a.query_cats, a.cw, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }

@@ -34,7 +34,10 @@
 //    lane binary-searches its own list per candidate insertion.
 
 #include <float.h>
+#include <type_traits>
 #include <hip/hip_runtime.h>
+
+#include "topk_common.h"
 
 #define TK_CHUNK 32   // items staged per LDS pass (32: fits 3 WGs/CU with K=20 lists)
 #define TK_MAXK 64    // max supported K
@@ -43,17 +46,6 @@
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ bool in_sorted(const int* arr, int n, int x) {
-  int lo = 0, hi = n - 1;
-  while (lo <= hi) {
-    int mid = (lo + hi) >> 1;
-    int v = arr[mid];
-    if (v == x) return true;
-    if (v < x) lo = mid + 1; else hi = mid - 1;
-  }
-  return false;
-}
 
 // PROF=true compiles in wall_clock64() phase accumulators (setup / item
 // staging / score+insert / writeback), summed per workgroup into
@@ -382,6 +374,40 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
   }
 }
 
+// Dynamic LDS of topk_score_kernel<f, *, cw> (layout at the top of its
+// body), floored for small K by the query-staging pass, which writes
+// TK_UPB rows of ys before the lists are initialized.
+constexpr size_t tk_lds_bytes(int f, int K, int cw) {
+  const size_t need =
+      sizeof(float) * (TK_CHUNK * (f + 4)) +
+      sizeof(int) * (TK_CHUNK + TK_UPB) * cw +
+      (sizeof(float) + sizeof(int)) * TK_WAVES * TK_UPB * (K + 1);
+  const size_t stage_need = sizeof(float) * TK_UPB * (f + 4);
+  return need < stage_need ? stage_need : need;
+}
+
+// args = the kernel's arguments, in order
+template <int F, bool PROF, int CW, typename... Args>
+static void launch(dim3 grid, int K, hipStream_t stream, Args... args) {
+  launch_dyn_lds<topk_score_kernel<F, PROF, CW>>(
+      grid, dim3(256), tk_lds_bytes(F, K, CW), stream, args...);
+}
+
+// the binding rejects prof together with a category filter
+template <int F, typename... Args>
+static void launch_rank(bool prof, int cw, Args... args) {
+  switch (cw) {
+    case 0:
+      if (prof) launch<F, true, 0>(args...);
+      else launch<F, false, 0>(args...);
+      break;
+    case 1: launch<F, false, 1>(args...); break;
+    case 2: launch<F, false, 2>(args...); break;
+    case 4: launch<F, false, 4>(args...); break;
+    default: break;
+  }
+}
+
 extern "C" void launch_topk_score(
     const float* Xq, const float* Y, const uint8_t* item_mask,
     const long long* ban_indptr, const int* ban_indices,
@@ -391,64 +417,20 @@ extern "C" void launch_topk_score(
     const int* item_cats, const int* query_cats, int cw,
     hipStream_t stream)
 {
-  dim3 grid(n_slices, (B + TK_UPB - 1) / TK_UPB);
-  dim3 block(256);
-  /* category filter (cw > 0): PROF=false only; the binding rejects prof  */
-  /* together with cats                                                   */
-#define LAUNCH_CATS(FF, CWV)                                                \
-  hipLaunchKernelGGL((topk_score_kernel<FF, false, CWV>), grid, block,      \
-                     lds_bytes, stream, Xq, Y, item_mask, ban_indptr,       \
-                     ban_indices, out_val, out_idx, B, N, K, n_slices,      \
-                     item_base, nullptr, item_cats, query_cats)
-#define LAUNCH(FF)                                                          \
-  do {                                                                      \
-    size_t lds_bytes =                                                      \
-        sizeof(float) * (TK_CHUNK * (FF + 4)) +                             \
-        sizeof(int) * (TK_CHUNK + TK_UPB) * cw +                            \
-        (sizeof(float) + sizeof(int)) * TK_WAVES * TK_UPB * (K+1);        \
-    /* small-K floor: the query-staging pass writes TK_UPB rows     */  \
-    const size_t stage_need = sizeof(float) * TK_UPB * (FF + 4);        \
-    if (lds_bytes < stage_need) lds_bytes = stage_need;                 \
-    static bool attr_set_##FF = false;                                      \
-    if (!attr_set_##FF && lds_bytes > 64 * 1024) {                          \
-      hipFuncSetAttribute(                                                  \
-          reinterpret_cast<const void*>(&topk_score_kernel<FF, false>),     \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      hipFuncSetAttribute(                                                  \
-          reinterpret_cast<const void*>(&topk_score_kernel<FF, true>),      \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      hipFuncSetAttribute(                                                  \
-          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 1>),  \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      hipFuncSetAttribute(                                                  \
-          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 2>),  \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      hipFuncSetAttribute(                                                  \
-          reinterpret_cast<const void*>(&topk_score_kernel<FF, false, 4>),  \
-          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);          \
-      attr_set_##FF = true;                                             \
-    }                                                                       \
-    if (cw == 1) LAUNCH_CATS(FF, 1);                                        \
-    else if (cw == 2) LAUNCH_CATS(FF, 2);                                   \
-    else if (cw == 4) LAUNCH_CATS(FF, 4);                                   \
-    else if (prof != nullptr)                                               \
-      hipLaunchKernelGGL((topk_score_kernel<FF, true>), grid, block,        \
-                         lds_bytes, stream, Xq, Y, item_mask, ban_indptr,   \
-                         ban_indices, out_val, out_idx, B, N, K, n_slices,  \
-                         item_base, prof, nullptr, nullptr);                \
-    else                                                                    \
-      hipLaunchKernelGGL((topk_score_kernel<FF, false>), grid, block,       \
-                         lds_bytes, stream, Xq, Y, item_mask, ban_indptr,   \
-                         ban_indices, out_val, out_idx, B, N, K, n_slices,  \
-                         item_base, nullptr, nullptr, nullptr);             \
-  } while (0)
+  const dim3 grid(n_slices, (B + TK_UPB - 1) / TK_UPB);
+  // the rank arrives as a compile-time tag so the argument list is
+  // written once
+  auto go = [&](auto rank) {
+    launch_rank<decltype(rank)::value>(
+        prof != nullptr, cw, grid, K, stream, Xq, Y, item_mask, ban_indptr,
+        ban_indices, out_val, out_idx, B, N, K, n_slices, item_base, prof,
+        item_cats, query_cats);
+  };
   switch (f) {
-    case 16: LAUNCH(16); break;
-    case 32: LAUNCH(32); break;
-    case 64: LAUNCH(64); break;
-    case 128: LAUNCH(128); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    case 32: go(std::integral_constant<int, 32>{}); break;
+    case 64: go(std::integral_constant<int, 64>{}); break;
+    case 128: go(std::integral_constant<int, 128>{}); break;
     default: break;
   }
-#undef LAUNCH
-#undef LAUNCH_CATS
 }

@@ -184,6 +184,24 @@ def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     return vals, idxs
 
 
+def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int) -> int:
+    """Item slices for the MFMA kernel: just enough to fill the chip
+    ONCE. The resident-WG count depends on the kernel's LDS (64-item
+    tile + the per-query top-K lists), so the target shrinks for large
+    K — a 1536-WG grid at K=64 only fits 768 at a time and the second
+    pass doubled the time (profiles/serve_k_sweep_r2.log). W = category
+    words per item (0 = no filter)."""
+    ublocks = (B + 63) // 64
+    # the kernel's dynamic LDS: tm_lds_bytes in csrc/topk_mfma.hip
+    lds = 64 * 2 * pf + 8 * 64 * (K + 1) + 4 * 64
+    if W:
+        # staged item category words (rows padded by 32/W words for
+        # W > 1) + the queries' accepted words
+        lds += W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
+    target = 256 * max(1, min(6, (160 * 1024) // lds))
+    return max(2, min(target // ublocks, (N + 255) // 256))
+
+
 def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                      item_mask, ban_indptr, ban_indices,
                      n_slices: Optional[int],
@@ -203,23 +221,8 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     pf = _mfma_rank(f)
     Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
     if n_slices is None:
-        # just enough slices to fill the chip ONCE: the resident-WG
-        # count depends on the kernel's LDS (64-item tile + the
-        # per-query top-K lists), so the target shrinks for large K —
-        # a 1536-WG grid at K=64 only fits 768 at a time and the
-        # second pass doubled the time (profiles/serve_k_sweep_r2.log)
-        # (the category path always runs the default 64-query variant)
-        upw = 128 if (os.environ.get("PIO_TOPK_QB") == "2"
-                      and item_cats is None) else 64
-        ublocks = (B + upw - 1) // upw
-        lds = 64 * 2 * pf + 8 * (upw // 64) * 64 * (K + 1) + 4 * 64
-        if item_cats is not None:
-            # staged item category words (rows padded by 32/W words
-            # for W > 1) + the queries' accepted words
-            W = item_cats.shape[1]
-            lds += W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
-        target = 256 * max(1, min(6, (160 * 1024) // lds))
-        n_slices = max(2, min(target // ublocks, (N + 255) // 256))
+        W = item_cats.shape[1] if item_cats is not None else 0
+        n_slices = _mfma_default_slices(B, N, pf, K, W)
     # Y's bf16 copy is cached (factors are static across serving batches);
     # Xq is cast per call — it changes every batch, and under hipGraph
     # capture (GraphedTopK) the cast must be part of the captured work

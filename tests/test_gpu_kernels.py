@@ -192,6 +192,35 @@ class TestTopKKernel:
         # bf16-near-tie at the candidate cut
         assert torch.allclose(gv, rv, atol=5e-3, rtol=5e-3)
 
+    def test_mfma_prof_variant_matches_live(self, monkeypatch):
+        """The MFMA PROF=true instantiation must emit bit-identical raw
+        candidates to the live one and fill prof[5]. Without the
+        cross-slice exchange (PIO_TOPK_GTH=0) every list is owned by one
+        wave and filled in program order, so the raw output is
+        deterministic. B=70: two query blocks, the second partial;
+        N=1000 is no multiple of 64 or of the 3 slices, so every slice
+        ends in a tail chunk."""
+        from predictionio_amd.ops import hip_ext
+        monkeypatch.setenv("PIO_TOPK_GTH", "0")
+        g = torch.Generator().manual_seed(29)
+        B, N, f, K, ns, nb = 70, 1000, 32, 5, 3, 4
+        Xq = torch.randn((B, f), generator=g).bfloat16().cuda()
+        Y = torch.randn((N, f), generator=g).bfloat16().cuda()
+        mask = (torch.rand(N, generator=g) < 0.2).to(torch.uint8).cuda()
+        bi = (torch.arange(B + 1, dtype=torch.int64) * nb).cuda()
+        bx = torch.sort(torch.randint(0, N, (B, nb), generator=g,
+                                      dtype=torch.int32), dim=1)[0]
+        bx = bx.reshape(-1).cuda()
+        ext = hip_ext()
+        v0, i0 = ext.topk_score_mfma(Xq, Y, K, ns, mask, bi, bx, 0)
+        prof = torch.zeros(5, dtype=torch.uint64, device="cuda")
+        v1, i1 = ext.topk_score_mfma(Xq, Y, K, ns, mask, bi, bx, 0, prof)
+        torch.cuda.synchronize()
+        assert torch.equal(v0, v1) and torch.equal(i0, i1)
+        p = prof.cpu().tolist()
+        assert p[4] == 2 * ns  # one sample per workgroup
+        assert all(t > 0 for t in p[:4])  # every phase ticked
+
     @pytest.mark.parametrize("gth", ["0", "1"])
     def test_mfma_gth_modes_match_fp32(self, gth, monkeypatch):
         """Cross-slice global-threshold exchange (PIO_TOPK_GTH) on AND

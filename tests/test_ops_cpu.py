@@ -248,6 +248,55 @@ class TestBf16Cache:
         assert r() is None  # weak keying: no leak of the fp32 factors
 
 
+class TestMfmaDefaultSlices:
+    """The MFMA wrapper's default n_slices. Expected values are worked
+    by hand from the formula (kernel LDS = 128*pf + 512*(K+1) + 256
+    bytes, plus W*(64 + 32/W [W > 1])*4 + 256*W with a category filter;
+    target = 256 * min(6, 160 KB // LDS) workgroups; n_slices =
+    max(2, min(target // ceil(B/64), ceil(N/256))))."""
+
+    def test_bench_shape(self):
+        # LDS = 8192 + 10752 + 256 = 19200; 163840 // 19200 = 8 -> 6;
+        # target 1536; 64 query blocks -> 24 (item cap 39063 is slack)
+        assert topk_ops._mfma_default_slices(4096, 10_000_000, 64, 20,
+                                             0) == 24
+
+    def test_category_words_count_towards_lds(self):
+        # LDS = 8192 + 512*44 + 256 = 30976; 163840 // 30976 = 5;
+        # target 1280; 16 query blocks -> 80 (item cap 3907 is slack)
+        assert topk_ops._mfma_default_slices(1000, 1_000_000, 64, 43,
+                                             0) == 80
+        # W=4 adds 4*72*4 + 1024 = 2176 -> 33152; 163840 // 33152 = 4;
+        # target 1024 -> 64
+        assert topk_ops._mfma_default_slices(1000, 1_000_000, 64, 43,
+                                             4) == 64
+
+    def test_wrapper_ignores_retired_qb_hook(self, monkeypatch):
+        """PIO_TOPK_QB=2 used to size the grid for 128-query workgroups
+        (here: 1 query block, LDS 10496 -> n_slices capped at 782). The
+        wrapper must pass the 64-query value whatever the environment
+        says: LDS = 4096 + 3072 + 256 = 7424 -> 6 WGs/CU, target 1536,
+        2 query blocks -> 768."""
+        from predictionio_amd import ops
+        monkeypatch.setenv("PIO_TOPK_QB", "2")
+        seen = []
+
+        class FakeExt:
+            @staticmethod
+            def topk_score_mfma(Xq, Y, K, n_slices, *a, **kw):
+                seen.append(n_slices)
+                shape = (Xq.shape[0], n_slices * K)
+                return (torch.full(shape, torch.finfo(torch.float32).min),
+                        torch.full(shape, -1, dtype=torch.int32))
+
+        monkeypatch.setattr(ops, "hip_ext", lambda: FakeExt)
+        B, N, f, K = 70, 200_000, 8, 5
+        topk_ops._topk_score_mfma(torch.randn(B, f), torch.randn(N, f), K,
+                                  None, None, None, None)
+        assert seen == [768]
+        assert topk_ops._mfma_default_slices(B, N, 32, K, 0) == 768
+
+
 class TestALSCheckpoint:
     def test_resume_matches_uninterrupted(self, tmp_path):
         import torch
