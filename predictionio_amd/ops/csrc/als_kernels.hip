@@ -31,6 +31,32 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+
+// two fused multiply-adds on an aligned register pair: one v_pk_fma_f32
+__device__ __forceinline__ f32x2_t fma2(f32x2_t a, f32x2_t b, f32x2_t c) {
+  return __builtin_elementwise_fma(a, b, c);
+}
+
+// Wave-uniform helpers for the one-wave-per-row solvers. The compiler
+// cannot prove threadIdx.x >> 6 (or anything loaded through it) uniform,
+// so every `k < n` test on the row degree became an exec-mask branch;
+// readfirstlane moves the value to an SGPR and the tests become s_cmp.
+__device__ __forceinline__ int uniform_i32(int v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ long long uniform_i64(long long v) {
+  const unsigned int lo = (unsigned int)uniform_i32((int)(unsigned long long)v);
+  const unsigned int hi =
+      (unsigned int)uniform_i32((int)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+// Broadcast lane k's value, k a literal once the caller's loop is
+// unrolled: one v_readlane_b32 into an SGPR — no LDS crossbar trip and
+// no lgkmcnt wait (__shfl lowers to ds_bpermute_b32 + s_waitcnt).
+__device__ __forceinline__ float lane_bcast(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
 
 
 template <int F>
@@ -322,8 +348,9 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
 // per-row solve cost dominates). This version assigns one 64-lane wave per
 // output row (2 waves per workgroup), keeps the Gramian in REGISTERS during
 // accumulation, and factorizes with the computed L columns persisted in LDS:
-//   - lane j owns row j of the FxF Gramian: acc[F] VGPRs, literal-indexed
-//     via fully unrolled loops (runtime-indexed register arrays spill).
+//   - lane j owns row j of the FxF Gramian: F VGPRs held as aligned pairs
+//     (ap[F/2]), literal-indexed via fully unrolled loops (runtime-indexed
+//     register arrays spill).
 //   - Cholesky: per step k the scaled pivot column is written to a per-wave
 //     LDS matrix Lc[k][*] (broadcast reads are conflict-free); no
 //     __syncthreads — waves are free-running, intra-wave LDS ordering is
@@ -350,8 +377,19 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
 // redistributes D's fragment layout (col = lane&15) into the solver's
 // lane-as-column acc[F]. Opt-in via PIO_ALS_STAGE_BF16 (same umbrella
 // as the Woodbury bf16 staging; b and the Cholesky stay fp32).
+// Waves per SIMD the wave kernel is compiled for. Without a floor the
+// register allocator spends the 512-register budget of a 128-thread
+// block freely (F = 16 came out at 110 registers where 58 do, the
+// F = 64 BF16G variant at 264 = one wave per SIMD). The floors sit at
+// or above the occupancy each rank had with plain __launch_bounds__(128)
+// (F = 16: 69 VGPRs, F = 32: 221, F = 64: 163 / 256 with BF16G).
+constexpr int wave_kernel_min_waves(int f) {
+  return f <= 16 ? 6 : (f <= 32 ? 4 : 2);
+}
+
 template <int F, bool BF16G = false>
-__global__ __launch_bounds__(128) void als_solve_wave_kernel(
+__global__ __launch_bounds__(128, wave_kernel_min_waves(F))
+void als_solve_wave_kernel(
     const long long* __restrict__ indptr,
     const int* __restrict__ indices,
     const float* __restrict__ values,
@@ -369,7 +407,8 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
   static_assert(F <= 64, "wave kernel supports rank <= 64");
   static_assert(!BF16G || F == 64, "MFMA Gramian variant needs F=64");
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // per WAVE, not per workgroup: the two waves hold different rows
+  const int wave = uniform_i32((int)(threadIdx.x >> 6));
 
   constexpr int PD = 4;  // global-load pipeline depth (latency hiding).
   // PD=8 and PD=12 MEASURED SLOWER (round 2: nnz=200 23.2->23.9/26.8 ms
@@ -387,14 +426,24 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
 
   for (long long row = (long long)blockIdx.x * 2 + wave; row < n_rows;
        row += (long long)gridDim.x * 2) {
-    const long long start = indptr[row];
-    const int nnz = (int)(indptr[row + 1] - start);
+    const long long start = uniform_i64(indptr[row]);
+    const int nnz = uniform_i32((int)(indptr[row + 1] - start));
     if (nnz <= skip_below || nnz > skip_above)
       continue;  // Woodbury / workgroup kernels own these rows
 
-    float acc[F];
+    // ln == lane, but tied to this row's start so the per-k lane compares
+    // of the solve are formed where they are used: hoisted out of the row
+    // loop, the 3*F exec masks overflow the SGPR file and get spilled to
+    // VGPR lanes (v_writelane/v_readlane on every use)
+    const int ln = lane | (int)(start >> 63);   // start >= 0
+
+    // the lane's row of the normal matrix, element m = ap[m >> 1][m & 1]:
+    // ALIGNED register pairs, so the Gramian and the Cholesky trailing
+    // update are v_pk_fma_f32 on fixed pairs (pairs that start at k + 1
+    // re-align the whole row with v_movs at every even k)
+    f32x2_t ap[F / 2];
 #pragma unroll
-    for (int m = 0; m < F; ++m) acc[m] = 0.f;
+    for (int m = 0; m < F / 2; ++m) ap[m] = f32x2_t{0.f, 0.f};
     float b_reg = 0.f;
 
     if constexpr (BF16G) {
@@ -465,7 +514,7 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
         wave_sync();
       }
       // redistribute D (col = lane&15, row = (lane>>4)*4 + r) into the
-      // solver's lane-as-column acc[F] through Lc (free until Cholesky)
+      // solver's lane-as-column ap[] row through Lc (free until Cholesky)
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
@@ -476,7 +525,7 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
                 accm[ti][tj][r];
       wave_sync();
 #pragma unroll
-      for (int m = 0; m < F; ++m) acc[m] = Lc[wave][m][lane];
+      for (int m = 0; m < F; ++m) ap[m >> 1][m & 1] = Lc[wave][m][lane];
       wave_sync();
     } else {
     // ---- Gramian accumulation (register row, LDS broadcast) ----
@@ -516,14 +565,13 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
         }
         b_reg = fmaf(w_b, ycur, b_reg);
         const float wyj = w_a * ycur;
+        const f32x2_t wyj2 = {wyj, wyj};
 #pragma unroll
         for (int q = 0; q < F / 4; ++q) {
-          const float4 y4 =
-              *reinterpret_cast<const float4*>(&ys[wave][p][4 * q]);
-          acc[4 * q + 0] = fmaf(wyj, y4.x, acc[4 * q + 0]);
-          acc[4 * q + 1] = fmaf(wyj, y4.y, acc[4 * q + 1]);
-          acc[4 * q + 2] = fmaf(wyj, y4.z, acc[4 * q + 2]);
-          acc[4 * q + 3] = fmaf(wyj, y4.w, acc[4 * q + 3]);
+          const f32x4_t y4 =
+              *reinterpret_cast<const f32x4_t*>(&ys[wave][p][4 * q]);
+          ap[2 * q + 0] = fma2(wyj2, y4.lo, ap[2 * q + 0]);
+          ap[2 * q + 1] = fma2(wyj2, y4.hi, ap[2 * q + 1]);
         }
         wave_sync();
       }
@@ -535,68 +583,81 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
     if (YtY != nullptr && lane < F) {
 #pragma unroll
       for (int q = 0; q < F / 4; ++q) {
-        const float4 t4 = *reinterpret_cast<const float4*>(
+        const f32x4_t t4 = *reinterpret_cast<const f32x4_t*>(
             &YtY[(long long)lane * F + 4 * q]);
-        acc[4 * q + 0] += t4.x;
-        acc[4 * q + 1] += t4.y;
-        acc[4 * q + 2] += t4.z;
-        acc[4 * q + 3] += t4.w;
+        ap[2 * q + 0] += t4.lo;
+        ap[2 * q + 1] += t4.hi;
       }
     }
     {
       const float reg = wr_scale ? lambda * (float)nnz : lambda;
 #pragma unroll
       for (int m = 0; m < F; ++m)
-        if (m == lane) acc[m] += reg;
+        if (m == ln) ap[m >> 1][m & 1] += reg;
     }
 
-    // ---- Cholesky (k-loop unrolled so acc[] stays in registers; each
-    //      finished column goes to LDS and acc[k] dies at step k) ----
+    // ---- Cholesky (k-loop unrolled so ap[] stays in registers; each
+    //      finished column goes to LDS and slot k dies at step k) ----
+    // The serial chain has no LDS-crossbar trip and no division: the
+    // pivot is a literal-lane v_readlane, L is kept STRICTLY lower (0 on
+    // and above the diagonal) and each lane keeps the reciprocal of its
+    // own diagonal, dl = 1 / L[lane][lane] — the rsqrt computed here.
+    float dl = 0.f;
 #pragma unroll
     for (int k = 0; k < F; ++k) {
-      float lkk = __shfl(acc[k], k);
-      // clamp so a singular (all-zero) row divides by a tiny nonzero pivot
-      // instead of 0 (empty rows must yield x = 0, not NaN)
+      float lkk = lane_bcast(ap[k >> 1][k & 1], k);
+      // clamp so a singular (all-zero) row multiplies by a huge finite
+      // 1/pivot instead of dividing by 0 (empty rows must yield x = 0,
+      // not NaN)
       lkk = lkk > 1e-30f ? lkk : 1e-30f;
       const float dinv = rsqrtf(lkk);
-      const float ljk = lane > k ? acc[k] * dinv
-                                 : (lane == k ? lkk * dinv : 0.f);
-      // persist column k: Lc[k][j] = L[j][k]. Guard: for F < 64 lanes
-      // >= F would write past the row into the next column. acc[k] is
-      // dead after this step — keep L[lane][k] in it so the forward
-      // solve runs from registers (round 2: the scalar Lc reads in the
+      const float ljk = ln > k ? ap[k >> 1][k & 1] * dinv : 0.f;
+      dl = ln == k ? dinv : dl;
+      // persist column k: Lc[k][j] = L[j][k]. For F < 64 lanes >= F
+      // would write past the row into the next column: they hold
+      // ljk = 0 and park it in the row's first pad column (LP = F + 4;
+      // no quad read reaches it). An exec-masked store here split every
+      // step into three blocks and F = 32 spilled. Slot k is dead after
+      // this step — keep L[lane][k] in it so the forward solve runs
+      // from registers (round 2: the scalar Lc reads in the
       // substitutions were the flagged ds_read_b32 round trips).
-      if (lane < F) Lc[wave][k][lane] = ljk;
-      acc[k] = ljk;
+      Lc[wave][k][lane < F ? lane : F] = ljk;
+      ap[k >> 1][k & 1] = ljk;
       wave_sync();
       // trailing update reading the pivot column in b128 QUADS: the
       // scalar version compiled to ds_read_b32 + s_waitcnt lgkmcnt(0)
       // per element — a full LDS round trip exposed F-k times per step
       // (seen in the ISA; the fixed per-row solve cost dominated the
       // kernel). One quad read amortizes the wait over 4 fmas.
+      // No per-lane guard: lanes <= k hold ljk = 0.
+      const f32x2_t nl2 = {-ljk, -ljk};
 #pragma unroll
       for (int m4 = (k + 1) & ~3; m4 < F; m4 += 4) {
-        const float4 lq =
-            *reinterpret_cast<const float4*>(&Lc[wave][k][m4]);
-        if (lane > k) {
-          if (m4 + 0 > k) acc[m4 + 0] = fmaf(-ljk, lq.x, acc[m4 + 0]);
-          if (m4 + 1 > k) acc[m4 + 1] = fmaf(-ljk, lq.y, acc[m4 + 1]);
-          if (m4 + 2 > k) acc[m4 + 2] = fmaf(-ljk, lq.z, acc[m4 + 2]);
-          if (m4 + 3 > k) acc[m4 + 3] = fmaf(-ljk, lq.w, acc[m4 + 3]);
+        const f32x4_t lq =
+            *reinterpret_cast<const f32x4_t*>(&Lc[wave][k][m4]);
+        const f32x2_t lh[2] = {lq.lo, lq.hi};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int m2 = m4 + 2 * h;
+          if (m2 > k)
+            ap[m2 >> 1] = fma2(nl2, lh[h], ap[m2 >> 1]);
+          else if (m2 == k)   // slot k itself now holds L[lane][k]
+            ap[m2 >> 1][1] = fmaf(-ljk, lh[h][1], ap[m2 >> 1][1]);
         }
       }
       wave_sync();
     }
 
-    // ---- forward solve L z = b — pure register/shfl chain: lane's row
-    //      L[lane][k] lives in acc[k], the pivot L[k][k] is lane k's
-    //      acc[k] (no LDS round trips on the serial chain) ----
+    // ---- forward solve L z = b — pure register chain: lane's row
+    //      L[lane][k] lives in slot k (0 for lane <= k), the pivot lane's
+    //      z_k = b * dl goes out by readlane; every lane scales by its dl
+    //      once at the end ----
 #pragma unroll
     for (int k = 0; k < F; ++k) {
-      const float zk = __shfl(b_reg, k) / __shfl(acc[k], k);
-      if (lane == k) b_reg = zk;
-      else if (lane > k) b_reg = fmaf(-acc[k], zk, b_reg);
+      const float zk = lane_bcast(b_reg * dl, k);
+      b_reg = fmaf(-ap[k >> 1][k & 1], zk, b_reg);
     }
+    b_reg *= dl;
     // ---- back solve L^T x = z: lane j needs L[k][j] = Lc[j][k], which
     //      is CONSECUTIVE over k at fixed row j — read b128 quads so one
     //      LDS round trip covers 4 serial steps ----
@@ -606,15 +667,13 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
       for (int k = F - 1; k >= 0; --k) {
         if ((k & 3) == 3 && lane < F)
           lq = *reinterpret_cast<const float4*>(&Lc[wave][lane][k & ~3]);
-        const float xk = __shfl(b_reg, k) / __shfl(acc[k], k);
-        if (lane == k) b_reg = xk;
-        else if (lane < k) {
-          const float lv = (k & 3) == 0 ? lq.x
-                           : (k & 3) == 1 ? lq.y
-                           : (k & 3) == 2 ? lq.z : lq.w;
-          b_reg = fmaf(-lv, xk, b_reg);
-        }
+        const float xk = lane_bcast(b_reg * dl, k);
+        const float lv = (k & 3) == 0 ? lq.x
+                         : (k & 3) == 1 ? lq.y
+                         : (k & 3) == 2 ? lq.z : lq.w;
+        b_reg = fmaf(ln < k ? -lv : 0.f, xk, b_reg);
       }
+      b_reg *= dl;
     }
 
     if (lane < F) X[row * (long long)F + lane] = b_reg;
@@ -665,7 +724,7 @@ __global__ __launch_bounds__(128) void als_solve_wave_kernel(
 // factor rounding at ~1e-5 relative ALS objective. Opt-in via
 // PIO_ALS_STAGE_BF16=1 (the V pointer then carries bf16 data).
 template <int F, int NW, int NLO, bool BF16S = false>
-__global__ __launch_bounds__(128, 6) void als_woodbury_kernel(
+__global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
     const long long* __restrict__ indptr,
     const int* __restrict__ indices,
     const float* __restrict__ values,
@@ -686,7 +745,8 @@ __global__ __launch_bounds__(128, 6) void als_woodbury_kernel(
   constexpr int FP = F + 4;    // fp32 row stride (floats)
   constexpr int FPH = F + 8;   // bf16 row stride (ushorts; 16B multiple)
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // per WAVE, not per workgroup: the two waves hold different rows
+  const int wave = uniform_i32((int)(threadIdx.x >> 6));
 
   __shared__ float Yl[2][NW][BF16S ? (FPH / 2) : FP];  // staged rows
   constexpr int MP = NW + 4;  // M row stride: 16B-aligned for b128 reads
@@ -701,8 +761,8 @@ __global__ __launch_bounds__(128, 6) void als_woodbury_kernel(
 
   for (long long row = (long long)blockIdx.x * 2 + wave; row < n_rows;
        row += (long long)gridDim.x * 2) {
-    const long long start = indptr[row];
-    const int n = (int)(indptr[row + 1] - start);
+    const long long start = uniform_i64(indptr[row]);
+    const int n = uniform_i32((int)(indptr[row + 1] - start));
     if (n > NW || n <= NLO) continue;  // other variant / dense kernel
     if (n == 0 && NLO < 0) {
       for (int e = lane; e < F; e += 64)
@@ -816,66 +876,109 @@ __global__ __launch_bounds__(128, 6) void als_woodbury_kernel(
     // back in b128 QUADS — the pure-LDS version compiled to one
     // ds_read_b32 + s_waitcnt per element (the same exposed-round-trip
     // disease fixed in the dense wave kernel, 1.7x there). A pure-shfl
-    // variant without the quad reads measured slower (528 shfls); this
-    // hybrid keeps the accumulators in registers and amortizes the LDS
-    // latency 4-wide. Uniform `k < n` guards (no break) keep the k-loops
-    // unrollable so mr[] stays in registers.
-    float mr[NW];
+    // variant without the quad reads measured slower (528 shfls, each a
+    // ds_bpermute_b32 + lgkmcnt wait — LDS crossbar trips, not register
+    // moves); this hybrid keeps the accumulators in registers and
+    // amortizes the LDS latency 4-wide. Uniform `k < n` guards (no break) keep the k-loops
+    // unrollable so mr[] stays in registers; n is an SGPR, so each guard
+    // is a scalar compare + branch.
+    //
+    // The serial chain carries no LDS trip and no division: pivots and
+    // rhs elements are broadcast with literal-lane v_readlane, L is kept
+    // STRICTLY lower (0 on and above the diagonal) and each lane keeps
+    // the reciprocal of its own diagonal, dl = 1 / L[lane][lane] = the
+    // rsqrt the Cholesky step computed anyway. With zeros above the
+    // diagonal the trailing update and the forward solve need no
+    // per-lane guard (lanes <= k multiply by 0).
+    //
+    // ln == lane, but tied to this row's start so the per-k lane compares
+    // are formed where they are used: hoisted out of the row loop, the
+    // 3*NW exec masks overflowed the SGPR file and were spilled to VGPR
+    // lanes (v_writelane/v_readlane on every use).
+    const int ln = lane | (int)(start >> 63);   // start >= 0
+    // mr[j] = mp[j >> 1][j & 1]: the row lives in ALIGNED register pairs
+    // and the trailing update is written pair by pair, so it compiles to
+    // v_pk_fma_f32 on fixed pairs. (Left to the vectorizer, the pairs
+    // started at k + 1 and every even k re-aligned the row with v_movs.)
+    f32x2_t mp[NW / 2];
+    const float* mrow = &M[wave][lane < NW ? lane : NW - 1][0];
+    // lanes >= NW hold ljk = 0 and park it in the row's first pad column
+    // (MP = NW + 4; no quad read reaches it): the store needs no exec mask
+    const int wcol = lane < NW ? lane : NW;
 #pragma unroll
-    for (int q = 0; q < NW; ++q)
-      mr[q] = (lane < n && q < n) ? M[wave][lane][q] : 0.f;
+    for (int q = 0; q < NW / 4; ++q) {
+      // entries at column >= n are stale; they land in never-read slots
+      const f32x4_t r4 = *reinterpret_cast<const f32x4_t*>(&mrow[4 * q]);
+      mp[2 * q + 0] = lane < n ? r4.lo : f32x2_t{0.f, 0.f};
+      mp[2 * q + 1] = lane < n ? r4.hi : f32x2_t{0.f, 0.f};
+    }
     float t = lane < n ? tv[wave][lane] : 0.f;
+    float dl = 0.f;
     wave_sync();
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
       if (k < n) {
-        float mkk = __shfl(mr[k], k);
+        float mkk = lane_bcast(mp[k >> 1][k & 1], k);
         mkk = mkk > 1e-30f ? mkk : 1e-30f;
         const float dinv = rsqrtf(mkk);
-        const float ljk = lane > k ? mr[k] * dinv
-                                   : (lane == k ? mkk * dinv : 0.f);
-        mr[k] = ljk;
-        if (lane < NW) M[wave][k][lane] = ljk;  // column k stored as row k
+        const float ljk = ln > k ? mp[k >> 1][k & 1] * dinv : 0.f;
+        dl = ln == k ? dinv : dl;
+        mp[k >> 1][k & 1] = ljk;
+        M[wave][k][wcol] = ljk;   // column k stored as row k
         wave_sync();
+        const f32x2_t nl2 = {-ljk, -ljk};
 #pragma unroll
         for (int j4 = (k + 1) & ~3; j4 < NW; j4 += 4) {
-          if (j4 < n) {
-            const float4 q4 =
-                *reinterpret_cast<const float4*>(&M[wave][k][j4]);
-            if (lane > k) {
-              // elements with j >= n update never-read mr slots (safe)
-              if (j4 + 0 > k) mr[j4 + 0] = fmaf(-ljk, q4.x, mr[j4 + 0]);
-              if (j4 + 1 > k) mr[j4 + 1] = fmaf(-ljk, q4.y, mr[j4 + 1]);
-              if (j4 + 2 > k) mr[j4 + 2] = fmaf(-ljk, q4.z, mr[j4 + 2]);
-              if (j4 + 3 > k) mr[j4 + 3] = fmaf(-ljk, q4.w, mr[j4 + 3]);
-            }
+          // no `j4 < n` work-skip: row k was rewritten for all NW lanes
+          // just above, with 0 at j >= n, so quads past n update
+          // never-read slots — and the skip measured SLOWER at every
+          // degree (its branches cost more than the FMAs it saves)
+          const f32x4_t q4 =
+              *reinterpret_cast<const f32x4_t*>(&M[wave][k][j4]);
+          const f32x2_t qh[2] = {q4.lo, q4.hi};
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int j2 = j4 + 2 * h;
+            if (j2 > k)
+              mp[j2 >> 1] = fma2(nl2, qh[h], mp[j2 >> 1]);
+            else if (j2 == k)   // slot k itself now holds L[lane][k]
+              mp[j2 >> 1][1] = fmaf(-ljk, qh[h][1], mp[j2 >> 1][1]);
           }
         }
         wave_sync();
       }
     }
-    // forward solve L z = rhs (L[lane][k] = mr[k], registers)
+    // forward solve L z = rhs (L[lane][k] = mp slot k, registers): t holds
+    // rhs - sum, unscaled; the pivot lane's z_k = t * dl goes out by
+    // readlane and every lane scales once at the end
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
       if (k < n) {
-        const float lkk = __shfl(mr[k], k);
-        const float zk = __shfl(t, k) / lkk;
-        if (lane == k) t = zk;
-        else if (lane > k) t = fmaf(-mr[k], zk, t);
+        const float zk = lane_bcast(t * dl, k);
+        t = fmaf(-mp[k >> 1][k & 1], zk, t);
       }
     }
+    t *= dl;
     // back solve L^T s = z: L[k][lane] = M[lane][k] (row `lane` holds
-    // column `lane`)
+    // column `lane`) — the lane's whole row in NW/4 b128 reads into mp[],
+    // dead after the forward solve. Lanes >= NW read row NW-1 (in
+    // bounds) and never use it; entries the Cholesky did not write this
+    // row (k >= n) are only ever selected away.
     wave_sync();
+#pragma unroll
+    for (int q = 0; q < NW / 4; ++q) {
+      const f32x4_t r4 = *reinterpret_cast<const f32x4_t*>(&mrow[4 * q]);
+      mp[2 * q + 0] = r4.lo;
+      mp[2 * q + 1] = r4.hi;
+    }
 #pragma unroll
     for (int k = NW - 1; k >= 0; --k) {
       if (k < n) {
-        const float lkk = __shfl(mr[k], k);
-        const float xk = __shfl(t, k) / lkk;
-        if (lane == k) t = xk;
-        else if (lane < k) t = fmaf(-M[wave][lane][k], xk, t);
+        const float xk = lane_bcast(t * dl, k);
+        t = fmaf(ln < k ? -mp[k >> 1][k & 1] : 0.f, xk, t);
       }
     }
+    t *= dl;
     if (implicit_mode) t *= dv[wave][lane < n ? lane : 0];  // s = d t
     if (lane < n) tv[wave][lane] = t;
     wave_sync();
