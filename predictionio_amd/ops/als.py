@@ -26,6 +26,14 @@ def gramian(Y: torch.Tensor) -> torch.Tensor:
     return Y.t() @ Y
 
 
+def row_transform(A: torch.Tensor, W: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A[N, f] @ W[f, f] on the GPU's hand-written row-transform kernel
+    (fp32 in, fp32 accumulate). `out`, if given, is written in place."""
+    from predictionio_amd.ops import hip_ext
+    return hip_ext().als_row_transform(A.contiguous(), W.contiguous(), out)
+
+
 def woodbury_lv(Y: torch.Tensor, YtY: torch.Tensor,
                 lam: float) -> tuple:
     """(Linv, V): L = chol(YtY + lam I), Linv = L^-1, V = Y L^-T — per-half-iteration
@@ -41,7 +49,13 @@ def woodbury_lv(Y: torch.Tensor, YtY: torch.Tensor,
     # with a 10M-row rhs hit HIPBLAS_STATUS_ALLOC_FAILED at bench scale,
     # while hipBLASLt GEMMs of that shape are proven.
     Linv = torch.linalg.solve_triangular(L, eye, upper=False)
-    V = (Y @ Linv.mT).contiguous()  # row v_i = L^-1 y_i
+    # row v_i = L^-1 y_i. On GPU the streaming fp32-MFMA row-transform
+    # kernel (als_xform.hip) with W = Linv^T; the library GEMM ran this
+    # tall-skinny shape several times off the HBM roofline.
+    if Y.is_cuda:
+        V = row_transform(Y, Linv.mT.contiguous())
+    else:
+        V = (Y @ Linv.mT).contiguous()
     import os as _os
     if (_os.environ.get("PIO_ALS_STAGE_BF16") == "1" and Y.is_cuda):
         V = V.to(torch.bfloat16).contiguous()
@@ -64,8 +78,8 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
 
     On GPU, rows with nnz <= 32 take the Woodbury path (exact — the same
     linear system through the push-through identity). Implicit mode runs
-    three phases: the Woodbury kernel emits whitened Z rows, one rocBLAS
-    triangular solve maps Z -> X for all rows, then the dense kernel fills
+    three phases: the Woodbury kernel emits whitened Z rows, one
+    row-transform launch maps Z -> X = Z L^-1 for all rows, then the dense kernel fills
     the big (nnz > 32) rows directly.
 
     lv: optional precomputed (Linv, V) from prepare_lv() — hoist it when
@@ -122,11 +136,7 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
                               float(alpha), True, False, 1, None)
             # X = Z L^-1 for all rows (Woodbury rows hold z; big rows get
             # overwritten by the dense pass next)
-            if direct_out is not None:
-                X = direct_out
-                torch.matmul(Z, Linv, out=X)
-            else:
-                X = (Z @ Linv).contiguous()
+            X = row_transform(Z, Linv, out=direct_out)
             ext.als_solve(ip, ix, vv, Yp, YtYp, None, float(lam),
                           float(alpha), True, False, 2, X)
         else:

@@ -9,8 +9,8 @@
 //  - One 256-thread workgroup (4 wave64) per output row (user or item).
 //  - The row's rated factor vectors are staged through LDS in chunks;
 //    each thread register-tiles a TMxTM block of the FxF Gramian
-//    (fp32 accumulate — CDNA4 has no fp32 MFMA; the Gramian pass is
-//    VALU fp32 with ds_read_b128 vector LDS reads).
+//    (the Gramian pass is VALU fp32 with ds_read_b128 vector LDS reads;
+//    the Woodbury kernel's n x n Gramian uses the f32 MFMA at NW >= 24).
 //  - Cholesky factorization + triangular solves run in LDS on the same
 //    workgroup — the Gramian never touches HBM (saves 16 KB/row of
 //    HBM traffic at f=64).
@@ -32,6 +32,7 @@ __device__ __forceinline__ void wave_sync() {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 // two fused multiply-adds on an aligned register pair: one v_pk_fma_f32
 __device__ __forceinline__ f32x2_t fma2(f32x2_t a, f32x2_t b, f32x2_t c) {
@@ -752,7 +753,8 @@ __global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
   constexpr int MP = NW + 4;  // M row stride: 16B-aligned for b128 reads
   __shared__ float M[2][NW][MP];       // I+DGD (implicit) / G+regI (explicit)
   __shared__ float tv[2][NW];          // col ids, then rhs, then solution
-  __shared__ float dv[2][NW];          // D diagonal (implicit)
+  __shared__ __attribute__((aligned(16)))
+  float dv[2][NW];                     // D diagonal (implicit); b128 reads
 
   float* yl = &Yl[wave][0][0];
   unsigned short* ylh = reinterpret_cast<unsigned short*>(yl);
@@ -817,8 +819,72 @@ __global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
     // only, mirror on write. Pair index advances incrementally — no
     // per-iteration integer division.
     const float reg = wr_scale ? lambda * (float)n : lambda;
-    const int npairs = n * (n + 1) / 2;
-    {
+    // Which G build: the f32-MFMA tile for fp32 staging at NW >= 24, the
+    // VALU pair loop otherwise. At NW = 20 the MFMA build measured no
+    // faster (kernel trace 38.1 vs 37.5 ms per bench step; explicit mode
+    // 6.1 vs 5.9 ms per 2M rows): its G phase shrank 3x but the other
+    // waves' M-solves, which live on v_pk_fma_f32, slowed by as much
+    // while the matrix pipe was busy.
+    constexpr bool MFMA_G = !BF16S && NW >= 24;
+    if constexpr (MFMA_G) {
+      // fp32 staging: G = V_u . V_u^T as ONE 32x32 tile on the f32 matrix
+      // pipe (v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate, a k-ordered
+      // fmaf chain). For V.V^T the A and B fragments are the same register
+      // (lane l holds V[l&31][k = l>>5] for both), and a sum over k may
+      // visit k in any order, so lane l reads the b128 quad at
+      // k = 8q + 4(l>>5) and feeds its four elements to four MFMAs: F/8
+      // ds_read_b128 + F/2 MFMAs per row, every staged element read once
+      // (the pair loop below re-read both rows per (i, j): 107 KB of LDS
+      // reads per row at n=20, F=64 — that was the phase's bound).
+      // Lanes with (l&31) >= NW read row NW-1 (Yl has NW rows per wave).
+      // Rows >= n are stale; D[i][j] depends on row i and row j alone, so
+      // they only reach M entries with i >= n or j >= n, which the solve
+      // never uses.
+      const int gj = lane & 31, gh = lane >> 5;
+      const f32x4_t* vq = reinterpret_cast<const f32x4_t*>(
+          &yl[(gj < NW ? gj : NW - 1) * FP + 4 * gh]);
+      f32x16_t acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
+                      0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < F / 8; ++q) {
+        const f32x4_t a = vq[2 * q];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, a.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, a.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, a.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, a.w, acc, 0, 0, 0);
+      }
+      // C/D layout: col = lane&31, row = (reg&3) + 8(reg>>2) + 4(lane>>5);
+      // by symmetry acc[4b..4b+3] is the contiguous quad
+      // G[gj][8b+4gh .. +3] of M's row gj: one ds_write_b128 per b.
+      // Stores only for gj < NW (rows past that are the other wave's M, or
+      // tv/dv) and only quads starting below NW (NW % 4 == 0, so such a
+      // quad ends inside the row).
+      static_assert(NW % 4 == 0 && NW <= 32, "one 32x32 tile, whole quads");
+      // Branch-free epilogue: in explicit mode dv is never written, so its
+      // (arbitrary) contents are selected away, not multiplied by zero.
+      const float dj = dv[wave][gj < NW ? gj : NW - 1];
+      const float dg = implicit_mode ? 1.f : reg;
+      f32x4_t dadd;   // the diagonal's addend, at the lane's slot of a quad
+#pragma unroll
+      for (int t = 0; t < 4; ++t) dadd[t] = (gj & 3) == t ? dg : 0.f;
+#pragma unroll
+      for (int b = 0; b < (NW + 7) / 8; ++b) {
+        const int c0 = 8 * b + 4 * gh;
+        if (gj < NW && c0 < NW) {
+          const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(&dv[wave][c0]);
+          const bool diag = (gj >> 2) == 2 * b + gh;
+          f32x4_t m4;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const float sc = implicit_mode ? dj * d4[t] : 1.f;
+            m4[t] = acc[4 * b + t] * sc + (diag ? dadd[t] : 0.f);
+          }
+          *reinterpret_cast<f32x4_t*>(&M[wave][gj][c0]) = m4;
+        }
+      }
+    } else {
+      // VALU build: the upper triangle only, mirrored on write
+      const int npairs = n * (n + 1) / 2;
       // map lane → first (i, j) with j >= i in the flattened triangle
       int p = lane, i = 0;
       while (p >= n - i && i < n) { p -= n - i; ++i; }

@@ -17,6 +17,10 @@ extern "C" void launch_als_solve(
     int implicit_mode, int wr_scale, int which,
     unsigned long long* prof, hipStream_t stream);
 
+extern "C" void launch_als_row_transform(
+    const float* in, const float* W, float* out, long long n_rows, int f,
+    int n_cu, hipStream_t stream);
+
 extern "C" void launch_topk_score(
     const float* Xq, const float* Y, const uint8_t* item_mask,
     const long long* ban_indptr, const int* ban_indices,
@@ -207,6 +211,44 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
   return X;
 }
 
+// out[N, f] = in[N, f] . W[f, f] in exact fp32 on the matrix pipe (see
+// als_xform.hip): the whitening V = Y L^-T and the map back X = Z L^-1.
+// `out` may be a row slice of a larger buffer, or `in` itself.
+torch::Tensor als_row_transform(torch::Tensor in, torch::Tensor W,
+                                c10::optional<torch::Tensor> out) {
+  check_cuda_f32(in, "in");
+  check_cuda_f32(W, "W");
+  TORCH_CHECK(in.dim() == 2 && W.dim() == 2, "in and W must be 2-D");
+  const int64_t n_rows = in.size(0);
+  const int64_t f = in.size(1);
+  TORCH_CHECK(supported_rank(f), "rank must be one of 16/32/64/128, got ", f);
+  TORCH_CHECK(W.size(0) == f && W.size(1) == f, "W must be f x f");
+  TORCH_CHECK(W.device() == in.device(), "W must be on in's device");
+  torch::Tensor X;
+  if (out.has_value()) {
+    check_cuda_f32(*out, "out");
+    TORCH_CHECK(out->dim() == 2 && out->size(0) == n_rows &&
+                    out->size(1) == f, "out must be n_rows x f");
+    TORCH_CHECK(out->device() == in.device(), "out must be on in's device");
+    X = *out;
+  } else {
+    X = torch::empty({n_rows, f}, in.options());
+  }
+  if (n_rows == 0) return X;
+  // the kernel moves rows in 16-byte quads
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(in.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0,
+              "in/out must be 16-byte aligned");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(in.device());
+  hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int n_cu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  launch_als_row_transform(in.data_ptr<float>(), W.data_ptr<float>(),
+                           X.data_ptr<float>(), (long long)n_rows, (int)f,
+                           n_cu, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return X;
+}
+
 // Fused masked top-K scoring: per-slice candidate groups; caller merges
 // with a small torch.topk. Returns (vals [B, n_slices*4*K], idx i32).
 std::tuple<torch::Tensor, torch::Tensor> topk_score(
@@ -317,6 +359,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("alpha") = 1.0, py::arg("implicit_mode") = false,
         py::arg("wr_scale") = true, py::arg("which") = 0,
         py::arg("out") = py::none(), py::arg("prof") = py::none());
+  m.def("als_row_transform", &als_row_transform,
+        "out[N, f] = in[N, f] . W[f, f], fp32 MFMA row transform",
+        py::arg("in_"), py::arg("W"), py::arg("out") = py::none());
   m.def("topk_score", &topk_score, "Fused masked top-K scoring",
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
