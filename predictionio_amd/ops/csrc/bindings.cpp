@@ -36,8 +36,12 @@ extern "C" void launch_topk_mfma(
     const int* ban_indices, float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof, unsigned* th_g,
-    const int* item_cats, const int* query_cats, int cw,
+    const int* item_cats, const int* query_cats, int cw, int interleave,
     hipStream_t stream);
+
+extern "C" void launch_topk_rescore(
+    const float* Xq, const float* Y, const int* idx, float* out,
+    long long B, int C, int f, hipStream_t stream);
 
 namespace {
 
@@ -288,7 +292,12 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
 // MFMA variant of topk_score: bf16 query/item factors (fp32 accumulate on
 // the matrix cores). Output is n_slices candidate groups of K per query
 // (topk_score emits n_slices*4); the Python wrapper merges and
-// fp32-rescores.
+// fp32-rescores. K is the per-slice list length. interleave = true deals
+// the 64-item chunks round-robin to the slices (slice s takes chunks s,
+// s + n_slices, ...) instead of one contiguous run each. gth: None keeps
+// the PIO_TOPK_GTH default, false launches without the cross-slice
+// threshold — it prunes to the top K overall, so a caller that wants
+// every slice's own top K (the union path) must turn it off.
 std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
     torch::Tensor Xq, torch::Tensor Y, int64_t K, int64_t n_slices,
     c10::optional<torch::Tensor> item_mask,
@@ -296,7 +305,8 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
     c10::optional<torch::Tensor> ban_indices, int64_t item_base,
     c10::optional<torch::Tensor> prof,
     c10::optional<torch::Tensor> item_cats,
-    c10::optional<torch::Tensor> query_cats) {
+    c10::optional<torch::Tensor> query_cats, bool interleave,
+    c10::optional<bool> gth_opt) {
   TORCH_CHECK(Xq.is_cuda() && Xq.is_contiguous() &&
                   Xq.scalar_type() == torch::kBFloat16,
               "Xq must be contiguous bf16 GPU");
@@ -311,6 +321,8 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   TORCH_CHECK(n_slices >= 1);
+  TORCH_CHECK(!(interleave && prof.has_value()),
+              "prof cannot be combined with interleave");
   const TopkArgs a = check_topk_args(item_mask, ban_indptr, ban_indices, prof,
                                      item_cats, query_cats, B, N);
   // one candidate group per slice per query (the kernel keeps a single
@@ -332,7 +344,8 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   torch::Tensor th_g;
   unsigned* th_g_ptr = nullptr;
   const char* e_gth = getenv("PIO_TOPK_GTH");
-  const bool gth = !(e_gth != nullptr && e_gth[0] == '0');
+  const bool gth = gth_opt.has_value()
+      ? *gth_opt : !(e_gth != nullptr && e_gth[0] == '0');
   if (gth) {
     th_g = torch::zeros({B}, Xq.options().dtype(torch::kInt32));
     th_g_ptr = reinterpret_cast<unsigned*>(th_g.data_ptr<int>());
@@ -343,9 +356,44 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
       a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
       out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f, (int)K,
       (int)n_slices, (int)item_base, a.prof, th_g_ptr, a.item_cats,
-      a.query_cats, a.cw, stream);
+      a.query_cats, a.cw, interleave ? 1 : 0, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
+}
+
+// out[b, c] = dot(Xq[b, :], Y[idx[b, c], :]) in fp32; idx < 0 gives -inf.
+// Any rank: rows move as float4 when f % 4 == 0 and both base pointers
+// are 16-byte aligned, as single floats otherwise. The kernel trusts
+// idx, so the upper bound is checked here (one small reduction).
+torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
+                           torch::Tensor idx) {
+  check_cuda_f32(Xq, "Xq");
+  check_cuda_f32(Y, "Y");
+  TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2 && idx.dim() == 2,
+              "Xq, Y and idx must be 2-D");
+  TORCH_CHECK(Xq.size(1) == Y.size(1), "Xq/Y rank mismatch");
+  TORCH_CHECK(idx.is_cuda() && idx.is_contiguous() &&
+                  idx.scalar_type() == torch::kInt32,
+              "idx must be a contiguous i32 GPU tensor");
+  TORCH_CHECK(Y.device() == Xq.device() && idx.device() == Xq.device(),
+              "Xq, Y and idx must be on one device");
+  const int64_t B = Xq.size(0);
+  const int64_t C = idx.size(1);
+  TORCH_CHECK(idx.size(0) == B, "idx must have one row per query");
+  TORCH_CHECK(C < (1LL << 31) && B * C <= (1LL << 34),
+              "too many candidates for one launch");
+  auto out = torch::empty({B, C}, Xq.options());
+  if (B * C == 0) return out;
+  TORCH_CHECK(idx.max().item<int>() < Y.size(0),
+              "idx holds an index >= the number of items");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_topk_rescore(Xq.data_ptr<float>(), Y.data_ptr<float>(),
+                      idx.data_ptr<int>(), out.data_ptr<float>(),
+                      (long long)B, (int)C, (int)Xq.size(1), stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return out;
 }
 
 }  // namespace
@@ -374,5 +422,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
         py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
-        py::arg("query_cats") = py::none());
+        py::arg("query_cats") = py::none(), py::arg("interleave") = false,
+        py::arg("gth") = py::none());
+  m.def("topk_rescore", &topk_rescore,
+        "Exact fp32 dots of each query with its shortlisted items",
+        py::arg("Xq"), py::arg("Y"), py::arg("idx"));
 }

@@ -118,7 +118,16 @@ __device__ __forceinline__ float tm_dec(unsigned k) {
 // TM_CHUNK x CW words ride the same register-staged pipeline as the Y
 // tile, into a word-major LDS image so a lane's four D rows are one b128.
 // Every CW > 0 line sits under `if constexpr`; CW == 0 is unchanged.
-template <int F, bool PROF, int CW = 0>
+//
+// ILV = true interleaves the slices at chunk granularity: slice s takes
+// the TM_CHUNK-item chunks s, s + n_slices, s + 2 n_slices, ... of the
+// whole item range instead of one contiguous run. The union path for
+// K > 64 (ops/topk.py) needs it: item ids follow first appearance, so the
+// popular, large-norm items cluster at low ids and a contiguous slice
+// would hold far more than its share of a query's best items. A slice
+// past the last chunk loads nothing and writes K empty slots. Every ILV
+// line is a compile-time branch; ILV == false is unchanged.
+template <int F, bool PROF, int CW = 0, bool ILV = false>
 __global__ __launch_bounds__(TM_BS, 6)
 void topk_mfma_kernel(
     const unsigned short* __restrict__ Xq,   // B x F bf16
@@ -142,6 +151,7 @@ void topk_mfma_kernel(
   static_assert(CW == 0 || CW == 1 || CW == 2 || CW == 4,
                 "category words per item must be 1, 2 or 4");
   static_assert(CW == 0 || !PROF, "no phase probe with the category filter");
+  static_assert(!ILV || !PROF, "no phase probe with interleaved slices");
   static_assert(TM_CHUNK * CW <= TM_BS,
                 "one staged category word per thread");
   constexpr int ROWB = F * 2;            // bytes per staged Y row
@@ -175,8 +185,9 @@ void topk_mfma_kernel(
   const bool has_user = guser < B;
   const int slice = blockIdx.y;
   const long long per = (N + n_slices - 1) / n_slices;
-  const long long it0 = (long long)slice * per;
-  const long long it1 = min(N, it0 + per);
+  const long long it0 =
+      ILV ? (long long)slice * TM_CHUNK : (long long)slice * per;
+  const long long it1 = ILV ? N : min(N, it0 + per);
 
   // ---- X fragments: one b128 per K-step, held for the whole kernel
   bf16x8 xf[KS];
@@ -303,11 +314,20 @@ void topk_mfma_kernel(
   // score, so the first fold is a no-op)
   unsigned gth_pipe =
       (th_g != nullptr && lg == 0 && has_user) ? th_g[guser] : 0u;
-  const int n_chunks = (int)((it1 - it0 + TM_CHUNK - 1) / TM_CHUNK);
-  load_stg(it0);
+  int n_chunks;
+  if constexpr (ILV) {
+    const long long nch = (N + TM_CHUNK - 1) / TM_CHUNK;
+    n_chunks =
+        slice < nch ? (int)((nch - slice + n_slices - 1) / n_slices) : 0;
+  } else {
+    n_chunks = (int)((it1 - it0 + TM_CHUNK - 1) / TM_CHUNK);
+  }
+  // items between the starts of a slice's consecutive chunks
+  const long long cstep = ILV ? (long long)n_slices * TM_CHUNK : TM_CHUNK;
+  if (!ILV || n_chunks > 0) load_stg(it0);
 
   for (int ci = 0; ci < n_chunks; ++ci) {
-    const long long base = it0 + (long long)ci * TM_CHUNK;
+    const long long base = it0 + (long long)ci * cstep;
     __syncthreads();  // all waves done reading the previous chunk
     drain();
     // fold the cross-slice global threshold into the local one every
@@ -329,7 +349,11 @@ void topk_mfma_kernel(
     // issue the NEXT chunk's global loads AFTER the barrier (a
     // __syncthreads compiles to s_waitcnt vmcnt(0)) so they fly
     // under the MFMA phase
-    if (base + TM_CHUNK < it1) load_stg(base + TM_CHUNK);
+    if constexpr (ILV) {
+      if (ci + 1 < n_chunks) load_stg(base + cstep);
+    } else {
+      if (base + TM_CHUNK < it1) load_stg(base + TM_CHUNK);
+    }
     if (probe) {
       const unsigned long long now = wall_clock64();
       acc_stage += now - pt;
@@ -474,23 +498,30 @@ void topk_mfma_kernel(
 }
 
 // args = the kernel's arguments, in order
-template <int F, bool PROF, int CW, typename... Args>
+template <int F, bool PROF, int CW, bool ILV, typename... Args>
 static void launch(dim3 grid, int K, hipStream_t stream, Args... args) {
-  launch_dyn_lds<topk_mfma_kernel<F, PROF, CW>>(
+  launch_dyn_lds<topk_mfma_kernel<F, PROF, CW, ILV>>(
       grid, dim3(TM_BS), tm_lds_bytes(F, K, CW), stream, args...);
 }
 
-// the binding rejects prof together with a category filter
+template <int F, int CW, typename... Args>
+static void launch_cw(bool ilv, Args... args) {
+  if (ilv) launch<F, false, CW, true>(args...);
+  else launch<F, false, CW, false>(args...);
+}
+
+// the binding rejects prof together with a category filter or with
+// interleaved slices
 template <int F, typename... Args>
-static void launch_rank(bool prof, int cw, Args... args) {
+static void launch_rank(bool prof, int cw, bool ilv, Args... args) {
   switch (cw) {
     case 0:
-      if (prof) launch<F, true, 0>(args...);
-      else launch<F, false, 0>(args...);
+      if (prof) launch<F, true, 0, false>(args...);
+      else launch_cw<F, 0>(ilv, args...);
       break;
-    case 1: launch<F, false, 1>(args...); break;
-    case 2: launch<F, false, 2>(args...); break;
-    case 4: launch<F, false, 4>(args...); break;
+    case 1: launch_cw<F, 1>(ilv, args...); break;
+    case 2: launch_cw<F, 2>(ilv, args...); break;
+    case 4: launch_cw<F, 4>(ilv, args...); break;
     default: break;
   }
 }
@@ -501,7 +532,7 @@ extern "C" void launch_topk_mfma(
     const int* ban_indices, float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof, unsigned* th_g,
-    const int* item_cats, const int* query_cats, int cw,
+    const int* item_cats, const int* query_cats, int cw, int interleave,
     hipStream_t stream)
 {
   const dim3 grid((B + TM_UPB - 1) / TM_UPB, n_slices);
@@ -511,9 +542,9 @@ extern "C" void launch_topk_mfma(
   // written once
   auto go = [&](auto rank) {
     launch_rank<decltype(rank)::value>(
-        prof != nullptr, cw, grid, K, stream, Xq, Y, item_mask, ban_indptr,
-        ban_indices, out_val, out_idx, B, N, K, n_slices, item_base, prof,
-        th_g, kflags, item_cats, query_cats);
+        prof != nullptr, cw, interleave != 0, grid, K, stream, Xq, Y,
+        item_mask, ban_indptr, ban_indices, out_val, out_idx, B, N, K,
+        n_slices, item_base, prof, th_g, kflags, item_cats, query_cats);
   };
   switch (f) {
     case 32: go(std::integral_constant<int, 32>{}); break;

@@ -8,13 +8,17 @@ predictKnownUser/predictSimilar (ECommAlgorithm.scala:471-599).
 
 from __future__ import annotations
 
+import logging
+import math
 import os
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch.utils.weak import WeakTensorKeyDictionary
 
 from predictionio_amd.ops.als import pad_rank
+
+log = logging.getLogger(__name__)
 
 # cached bf16 copies of factor matrices for the MFMA scoring path,
 # keyed weakly by the fp32 tensor (invalidated on in-place writes via
@@ -53,7 +57,8 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                n_slices: Optional[int] = None,
                mode: Optional[str] = None,
                item_cats: Optional[torch.Tensor] = None,
-               query_cats: Optional[torch.Tensor] = None
+               query_cats: Optional[torch.Tensor] = None,
+               list_k: Optional[int] = None
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K of (Xq @ Y.T) per query row, with optional global item mask
     (uint8, 1=banned) and per-query banned lists (CSR int32, sorted).
@@ -69,20 +74,48 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     mode: "mfma" (default on GPU) scores on the matrix cores with bf16
     inputs / fp32 accumulate, then re-checks the surviving candidates
     against the fp32 factors so returned values are exact fp32 dots;
-    "fp32" forces the all-fp32 VALU kernel (v3). CPU ignores mode."""
+    "fp32" forces the all-fp32 VALU kernel (v3). CPU ignores mode.
+
+    64 < K <= 1024 in "mfma" mode takes the union path
+    (_topk_score_union): short per-slice lists over interleaved slices,
+    merged and re-scored in fp32. mode="union" forces that path at any
+    K >= 1 (ValueError when the shape admits no plan); list_k with
+    n_slices pins its plan. PIO_TOPK_UNION=0, mode="fp32", K > 1024 and
+    calls under stream capture keep the materialized fallback."""
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
     _check_cats(item_cats, query_cats, B, N)
     if Xq.is_cuda:
-        if K > 64:
-            # the fused kernels keep K-entry per-query lists in LDS and
-            # cap at 64; arbitrary `num` (the reference allows any) falls
-            # back to a materialized masked matmul + torch.topk on device
-            return _topk_torch_gpu(Xq, Y, K, item_mask, ban_indptr,
-                                   ban_indices, item_cats, query_cats)
         if mode is None:
             mode = os.environ.get("PIO_TOPK_MODE", "mfma")
+        if mode == "union":
+            if K < 1:
+                raise ValueError("K must be >= 1")
+            out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
+                                    ban_indices, n_slices, list_k,
+                                    item_cats, query_cats)
+            if out is None:
+                raise ValueError(
+                    f"no union plan for B={B}, N={N}, rank={f}, K={K}")
+            return out
+        if K > 64:
+            # the fused kernels keep per-query lists in LDS and cap them
+            # at 64 entries. Up to K = 1024 the union of many short lists
+            # stands in for one long one; it syncs with the host to read
+            # its flags, so not under stream capture
+            if (mode == "mfma" and K <= 1024
+                    and os.environ.get("PIO_TOPK_UNION", "1") != "0"
+                    and not torch.cuda.is_current_stream_capturing()):
+                out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
+                                        ban_indices, n_slices, list_k,
+                                        item_cats, query_cats)
+                if out is not None:
+                    return out
+            # arbitrary `num` (the reference allows any): a materialized
+            # masked matmul + torch.topk on device
+            return _topk_torch_gpu(Xq, Y, K, item_mask, ban_indptr,
+                                   ban_indices, item_cats, query_cats)
         if mode == "mfma" and _mfma_rank(f) is not None:
             return _topk_score_mfma(Xq, Y, K, item_mask, ban_indptr,
                                     ban_indices, n_slices,
@@ -154,8 +187,10 @@ def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                     item_mask, ban_indptr, ban_indices,
                     item_cats=None, query_cats=None
                     ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Device fallback for K > 64: materialized masked score matrix +
-    torch.topk. Memory: B x N fp32 — callers with huge B should batch."""
+    """Device fallback for K above what the fused paths take (K > 1024,
+    shapes without a union plan, flagged union queries): materialized
+    masked score matrix + torch.topk. Memory: B x N fp32 — callers with
+    huge B should batch."""
     scores = Xq @ Y.t()
     if item_cats is not None:
         scores = scores.masked_fill(_cats_miss(item_cats, query_cats),
@@ -200,6 +235,191 @@ def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int) -> int:
         lds += W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
     target = 256 * max(1, min(6, (160 * 1024) // lds))
     return max(2, min(target // ublocks, (N + 255) // 256))
+
+
+_UNION_LISTS = (16, 20, 24, 32, 40, 48, 64)
+_union_stats: Dict[str, int] = {"calls": 0, "queries": 0, "flagged": 0}
+
+
+def union_stats() -> Dict[str, int]:
+    """Cumulative counters of the union path since import: calls, queries
+    served, and queries whose flag sent them to the fallback."""
+    return dict(_union_stats)
+
+
+def _union_rule(L: int, S: int, M: int) -> bool:
+    """A slice expects mu = M / S of a query's top M (interleaved slices
+    make membership near-uniform). A FULL list flags its query whether or
+    not it dropped anything, so the tail that matters is P(X >= L):
+    L - 1 >= mu + 6 sqrt(mu) puts it below 1e-6 per slice (Poisson)."""
+    mu = M / S
+    return S * L >= M and L - 1 >= mu + 6.0 * math.sqrt(mu)
+
+
+def _union_min_slices(L: int, M: int) -> int:
+    """Smallest S that passes _union_rule for list length L."""
+    mu_max = (math.sqrt(8 + L) - 3.0) ** 2   # mu + 6 sqrt(mu) = L - 1
+    S = max(1, math.ceil(M / mu_max))
+    while not _union_rule(L, S, M):          # guard the float boundary
+        S += 1
+    return S
+
+
+def _union_plan(B: int, N: int, pf: int, K: int, W: int,
+                list_k: Optional[int] = None,
+                n_slices: Optional[int] = None
+                ) -> Optional[Tuple[int, int]]:
+    """(L, S) for the union path: per-slice list length L <= 64 and slice
+    count S, or None when the shape admits none (tiny N).
+
+    The SHORTEST list in _UNION_LISTS wins, with as many slices as it
+    takes: S = max(chip-filling count, smallest S passing _union_rule),
+    as long as S <= ceil(N / 64) (a slice needs a chunk). The sweep in
+    NOTES.md decided this: at equal S a shorter list is always faster
+    (the insert scan is O(L) and list LDS costs occupancy), and trading
+    list length for slices beyond one chip-filling wave still pays — at
+    B = 4096, K = 1024, (16, 512) runs in 84 ms against 331 ms for
+    (64, 67). 2 <= S <= ceil(N / 64) and S * L >= 2K always hold.
+    list_k / n_slices pin either half; a pinned pair is only
+    range-checked."""
+    M = 2 * K
+    nch = (N + 63) // 64
+    if nch < 2:
+        return None
+    if list_k is not None and not 1 <= list_k <= 64:
+        raise ValueError("list_k must be in [1, 64]")
+    if n_slices is not None:
+        if n_slices < 1:
+            raise ValueError("n_slices must be >= 1")
+        n_slices = max(2, min(int(n_slices), nch))
+    if list_k is not None and n_slices is not None:
+        return (int(list_k), n_slices) if n_slices * list_k >= M else None
+    for L in (_UNION_LISTS if list_k is None else (int(list_k),)):
+        if n_slices is not None:
+            if _union_rule(L, n_slices, M):
+                return L, n_slices
+            continue
+        S = max(2, _mfma_default_slices(B, N, pf, L, W),
+                _union_min_slices(L, M))
+        if S <= nch:
+            return L, S
+    return None
+
+
+def _union_merge(vals: torch.Tensor, idxs: torch.Tensor, L: int, S: int,
+                 M: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Top M of a query's S per-slice lists of length L, and the exact
+    test of whether that is the top M of all items.
+
+    vals / idxs [B, S*L]: slice-major candidate groups as the kernel
+    writes them, empty slots at -FLT_MAX / -1. Returns (short_idx [B,C]
+    int64, short_val [B,C], flagged [B] bool) with C = min(M, S*L);
+    invalid shortlist slots carry -1 / -inf.
+
+    A slice can only have dropped an item that belongs in the top M if
+    its list is full and even its smallest entry beats v_M, the M-th
+    best valid candidate of the union (-inf when fewer than M are
+    valid). Such a query is flagged; every other query's shortlist is
+    exactly the top M of the scores the lists were built from."""
+    B = vals.shape[0]
+    fmin = torch.finfo(torch.float32).min
+    C = min(M, S * L)
+    cv, pos = torch.topk(vals, C, dim=1)
+    ok = cv > fmin
+    short_idx = torch.gather(idxs, 1, pos).long().masked_fill(~ok, -1)
+    short_val = cv.masked_fill(~ok, float("-inf"))
+    if C == M:
+        v_m = short_val[:, M - 1]
+    else:
+        v_m = torch.full((B,), float("-inf"), device=vals.device)
+    smin = vals.view(B, S, L).min(dim=2).values   # > fmin iff list full
+    flagged = ((smin > fmin) & (smin > v_m.unsqueeze(1))).any(dim=1)
+    return short_idx, short_val, flagged
+
+
+def _select_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                rows: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The CSR (indptr, indices) restricted to `rows`, in that order."""
+    starts = indptr[rows]
+    lens = indptr[rows + 1] - starts
+    out_ptr = torch.zeros(rows.numel() + 1, dtype=indptr.dtype,
+                          device=indptr.device)
+    out_ptr[1:] = torch.cumsum(lens, 0)
+    total = int(out_ptr[-1])
+    src = (torch.repeat_interleave(starts - out_ptr[:-1], lens)
+           + torch.arange(total, device=indptr.device))
+    return out_ptr, indices[src]
+
+
+def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
+                      item_mask, ban_indptr, ban_indices,
+                      n_slices: Optional[int], list_k: Optional[int],
+                      item_cats=None, query_cats=None
+                      ) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+    """Union path for K above the kernel's list cap: ONE MFMA launch with
+    short lists (L <= 64, the kernel's tuned regime) over S slices
+    interleaved at chunk granularity, cross-slice threshold off; the
+    S*L candidates are merged to the bf16 top M = 2K, re-scored exactly
+    in fp32 by topk_rescore, and the top K of those returned — the same
+    "2K shortlist, fp32 re-check" contract as _topk_score_mfma. Queries
+    that _union_merge flags (some slice may have dropped a top-M item)
+    are recomputed by _topk_torch_gpu. None = no plan for this shape."""
+    from predictionio_amd.ops import hip_ext
+    B, f = Xq.shape
+    N = Y.shape[0]
+    pf = _mfma_rank(f)
+    if pf is None or B == 0:
+        return None
+    W = item_cats.shape[1] if item_cats is not None else 0
+    plan = _union_plan(B, N, pf, K, W, list_k, n_slices)
+    if plan is None:
+        return None
+    L, S = plan
+    M = 2 * K
+    ext = hip_ext()
+    Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
+    vals, idxs = ext.topk_score_mfma(
+        Xp.to(torch.bfloat16).contiguous(), bf16_copy(Y, pf), L, S,
+        item_mask.contiguous() if item_mask is not None else None,
+        ban_indptr.contiguous() if ban_indptr is not None else None,
+        ban_indices.contiguous() if ban_indices is not None else None, 0,
+        item_cats=item_cats, query_cats=query_cats,
+        interleave=True, gth=False)
+    short_idx, _, flagged = _union_merge(vals, idxs, L, S, M)
+    exact = ext.topk_rescore(Xq.contiguous(), Y.contiguous(),
+                             short_idx.to(torch.int32))
+    mv, p2 = torch.topk(exact, min(K, exact.shape[1]), dim=1)
+    midx = torch.gather(short_idx, 1, p2)
+    midx[mv == float("-inf")] = -1
+    if mv.shape[1] < K:  # pad like the reference
+        pad = K - mv.shape[1]
+        mv = torch.cat([mv, torch.full((B, pad), float("-inf"),
+                                       device=mv.device)], 1)
+        midx = torch.cat([midx, torch.full((B, pad), -1, dtype=midx.dtype,
+                                           device=midx.device)], 1)
+    rows = flagged.nonzero().flatten()
+    nf = rows.numel()
+    _union_stats["calls"] += 1
+    _union_stats["queries"] += B
+    _union_stats["flagged"] += nf
+    if nf:
+        if nf * 100 > B:
+            log.warning(
+                "top-K union path: %d of %d queries flagged (K=%d, L=%d, "
+                "S=%d) and recomputed by the materialized fallback", nf, B,
+                K, L, S)
+        blk = max(1, 2 ** 28 // N)  # <= 1 GiB of fp32 scores per block
+        for r0 in range(0, nf, blk):
+            r = rows[r0:r0 + blk]
+            bp = bi = None
+            if ban_indptr is not None:
+                bp, bi = _select_csr(ban_indptr, ban_indices, r)
+            fv, fi = _topk_torch_gpu(
+                Xq[r], Y, K, item_mask, bp, bi, item_cats,
+                query_cats[r] if query_cats is not None else None)
+            mv[r] = fv
+            midx[r] = fi
+    return mv, midx
 
 
 def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
