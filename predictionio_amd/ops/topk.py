@@ -72,16 +72,23 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     lists — an item must pass all three.
 
     mode: "mfma" (default on GPU) scores on the matrix cores with bf16
-    inputs / fp32 accumulate, then re-checks the surviving candidates
-    against the fp32 factors so returned values are exact fp32 dots;
-    "fp32" forces the all-fp32 VALU kernel (v3). CPU ignores mode.
+    inputs / fp32 accumulate, shortlists each query's best D valid items
+    by those scores, and re-scores the shortlist against the fp32
+    factors, so returned values are fp32 dots and an item of the fp32
+    top K is served whenever its bf16 rank among the valid items is at
+    most D. "fp32" forces the all-fp32 VALU kernel (v3), which is exact.
+    CPU ignores mode.
 
-    64 < K <= 1024 in "mfma" mode takes the union path
-    (_topk_score_union): short per-slice lists over interleaved slices,
-    merged and re-scored in fp32. mode="union" forces that path at any
-    K >= 1 (ValueError when the shape admits no plan); list_k with
-    n_slices pins its plan. PIO_TOPK_UNION=0, mode="fp32", K > 1024 and
-    calls under stream capture keep the materialized fallback."""
+    Eager "mfma" calls with K <= 1024 take the union path
+    (_topk_score_union) when the shape has a plan for it: short
+    per-slice lists over interleaved slices, merged to the exact bf16
+    top 2K (D = 2K). Otherwise K <= 64 runs the list kernel
+    (_topk_score_mfma) with D = min(2K, 64): shapes without a plan
+    (N <= 64 among them), calls under stream capture (the union path
+    syncs with the host) and PIO_TOPK_UNION=0. mode="union" forces the
+    union path at any K >= 1 (ValueError when the shape admits no plan);
+    list_k with n_slices pins its plan. K > 64 without the union path,
+    and any K > 1024, use the materialized fallback, which is exact."""
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
@@ -99,19 +106,20 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                 raise ValueError(
                     f"no union plan for B={B}, N={N}, rank={f}, K={K}")
             return out
+        # the eager mfma route at every K <= 1024 is the union path when
+        # the shape has a plan: many short per-slice lists stand in for
+        # one long one, and its shortlist is the exact bf16 top 2K where
+        # the list kernel's 64-entry LDS lists stop at 64. It syncs with
+        # the host to read its flags, so not under stream capture
+        if (mode == "mfma" and 1 <= K <= 1024
+                and os.environ.get("PIO_TOPK_UNION", "1") != "0"
+                and not torch.cuda.is_current_stream_capturing()):
+            out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
+                                    ban_indices, n_slices, list_k,
+                                    item_cats, query_cats)
+            if out is not None:
+                return out
         if K > 64:
-            # the fused kernels keep per-query lists in LDS and cap them
-            # at 64 entries. Up to K = 1024 the union of many short lists
-            # stands in for one long one; it syncs with the host to read
-            # its flags, so not under stream capture
-            if (mode == "mfma" and K <= 1024
-                    and os.environ.get("PIO_TOPK_UNION", "1") != "0"
-                    and not torch.cuda.is_current_stream_capturing()):
-                out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
-                                        ban_indices, n_slices, list_k,
-                                        item_cats, query_cats)
-                if out is not None:
-                    return out
             # arbitrary `num` (the reference allows any): a materialized
             # masked matmul + torch.topk on device
             return _topk_torch_gpu(Xq, Y, K, item_mask, ban_indptr,
@@ -356,12 +364,12 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                       n_slices: Optional[int], list_k: Optional[int],
                       item_cats=None, query_cats=None
                       ) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
-    """Union path for K above the kernel's list cap: ONE MFMA launch with
-    short lists (L <= 64, the kernel's tuned regime) over S slices
+    """Union path, the eager route at every K <= 1024: ONE MFMA launch
+    with short lists (L <= 64, the kernel's tuned regime) over S slices
     interleaved at chunk granularity, cross-slice threshold off; the
     S*L candidates are merged to the bf16 top M = 2K, re-scored exactly
-    in fp32 by topk_rescore, and the top K of those returned — the same
-    "2K shortlist, fp32 re-check" contract as _topk_score_mfma. Queries
+    in fp32 by topk_rescore, and the top K of those returned. The flag
+    test is exact, so the shortlist depth is D = 2K at any K. Queries
     that _union_merge flags (some slice may have dropped a top-M item)
     are recomputed by _topk_torch_gpu. None = no plan for this shape."""
     from predictionio_amd.ops import hip_ext
@@ -427,27 +435,37 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                      n_slices: Optional[int],
                      item_cats=None, query_cats=None
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """MFMA path: bf16 matrix-core scoring selects ~2K candidates per
-    query (masks/bans applied in-kernel), then the candidates are
-    re-scored exactly against the fp32 factors and the final top-K taken
-    on those exact values. bf16 rounding perturbs scores by ~0.4%
-    relative (profiles/bf16_numerics_study.txt: 99.7% top-20 overlap
-    before any margin), so with a 2x candidate margin + fp32 re-check the
-    served (item, score) pairs match the fp32 reference except for
-    pathological near-ties at the candidate cut."""
+    """List-kernel MFMA path (capture-safe, any N): bf16 matrix-core
+    scoring keeps a list of D = min(2K, 64) per item slice per query
+    (masks/bans/categories applied in-kernel, so filtered items take no
+    depth); the union of the lists holds the query's bf16 top D whatever
+    the slicing and whether or not the cross-slice threshold is on (it
+    prunes to the top D overall). The best 2K of them are re-scored
+    against the fp32 factors and the final top-K taken on those values.
+
+    Contract: an item of the fp32 top K is served if it is also in the
+    bf16 top D among the valid items. bf16 rounding perturbs scores by
+    ~0.4% relative, which on clustered factors moves items across the K
+    cut in most queries but hardly ever past 2K. For 32 < K <= 64 the
+    64-entry list cap leaves D = 64 < 2K here; the union path
+    (_topk_score_union) delivers D = 2K at every K."""
     from predictionio_amd.ops import hip_ext
     B, f = Xq.shape
     N = Y.shape[0]
     pf = _mfma_rank(f)
     Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
+    # the per-slice list length IS the shortlist depth: with a list of K
+    # a slice holding the bf16 top K + 1 drops the (K+1)-th, and the
+    # cross-slice threshold prunes the other slices to the top K too
+    depth = min(2 * K, 64)
     if n_slices is None:
         W = item_cats.shape[1] if item_cats is not None else 0
-        n_slices = _mfma_default_slices(B, N, pf, K, W)
+        n_slices = _mfma_default_slices(B, N, pf, depth, W)
     # Y's bf16 copy is cached (factors are static across serving batches);
     # Xq is cast per call — it changes every batch, and under hipGraph
     # capture (GraphedTopK) the cast must be part of the captured work
     vals, idxs = hip_ext().topk_score_mfma(
-        Xp.to(torch.bfloat16).contiguous(), bf16_copy(Y, pf), K,
+        Xp.to(torch.bfloat16).contiguous(), bf16_copy(Y, pf), depth,
         int(n_slices),
         item_mask.contiguous() if item_mask is not None else None,
         ban_indptr.contiguous() if ban_indptr is not None else None,

@@ -230,6 +230,9 @@ class TestTopKKernel:
         fires)."""
         from predictionio_amd.ops import topk as topk_ops
         monkeypatch.setenv("PIO_TOPK_GTH", gth)
+        # the exchange lives in the list kernel; eager calls would
+        # otherwise take the union path, which launches without it
+        monkeypatch.setenv("PIO_TOPK_UNION", "0")
         g = torch.Generator().manual_seed(11)
         B, N, K, f = 96, 300_000, 20, 64
         Xq = torch.randn((B, f), generator=g).float()

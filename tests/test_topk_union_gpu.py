@@ -271,10 +271,11 @@ class TestUnionEndToEnd:
         _check_e2e(q, K, gv, gi)
         assert set(gi[0].tolist()) <= set(hot.tolist())
 
-    def test_union_mode_below_the_cutover(self):
-        """mode="union" at K=20 returns the default path's items, and
-        values that are both the fp32 dots: each within the fp32
-        accumulation bound f 2^-23 (|x|.|y|) of the float64 dot."""
+    def test_union_mode_below_the_cutover(self, monkeypatch):
+        """mode="union" at K=20 returns the list kernel's items, the
+        eager default is the union path too, and all values are the
+        fp32 dots: each within the fp32 accumulation bound
+        f 2^-23 (|x|.|y|) of the float64 dot."""
         from predictionio_amd.ops import topk as topk_ops
         B, N, f, K = 37, 5000, 64, 20
         p = _problem(B, N, f)
@@ -282,8 +283,12 @@ class TestUnionEndToEnd:
         calls = topk_ops.union_stats()["calls"]
         uv, ui = topk_ops.topk_score(Xq, Y, K, mode="union")
         assert topk_ops.union_stats()["calls"] == calls + 1
+        ev, ei = topk_ops.topk_score(Xq, Y, K)
+        assert topk_ops.union_stats()["calls"] == calls + 2
+        assert torch.equal(ev, uv) and torch.equal(ei, ui)
+        monkeypatch.setenv("PIO_TOPK_UNION", "0")
         dv, di = topk_ops.topk_score(Xq, Y, K)
-        assert topk_ops.union_stats()["calls"] == calls + 1
+        assert topk_ops.union_stats()["calls"] == calls + 2
         assert torch.equal(ui.sort(dim=1).values, di.sort(dim=1).values)
         d64 = p["Xq"].double() @ p["Y"].double().t()
         bound = f * 2.0 ** -23 * (p["Xq"].abs().double()
