@@ -44,6 +44,24 @@ class ALSParams:
     checkpoint_dir: Optional[str] = None  # ALS every 10 iters to bound
                                 # lineage, ALSAlgorithm.scala:85; here it
                                 # is crash-resume for 100M-scale runs)
+    loss_every: int = 0         # >0: evaluate the training objective after
+                                # every N-th iteration (ALSTrainer.loss)
+    tol: float = 0.0            # >0: stop once an evaluation improves on
+                                # the one before by <= tol * |previous|;
+                                # implies loss_every = 1 if that is 0
+
+
+class _Gathered:
+    """A factor gather that has already finished: stands in for the
+    ChunkedGather in ALSTrainer._pending_y so that whoever consumes it
+    next (step, gather_factors, a checkpoint) gets the same tensor
+    without a second collective."""
+
+    def __init__(self, full: torch.Tensor):
+        self.full = full
+
+    def finish(self) -> torch.Tensor:
+        return self.full
 
 
 class ALSTrainer:
@@ -69,6 +87,7 @@ class ALSTrainer:
         self.Y: Optional[torch.Tensor] = None  # local item factors
         self._pending_y = None  # in-flight Y gather from the item half
         self.phase_times = {"gather_s": 0.0, "solve_s": 0.0}
+        self.loss_history: list = []  # fit()'s objective evaluations
 
     # ------------------------------------------------------------ data
 
@@ -208,6 +227,75 @@ class ALSTrainer:
             self.phase_times["gather_s"] += (t1 - t0) + (t3 - t2)
             self.phase_times["solve_s"] += (t2 - t1) + (t4 - t3)
 
+    # ----------------------------------------------------------- objective
+
+    def _full_y(self) -> torch.Tensor:
+        """The full Y the next user half-step will consume. An in-flight
+        gather is finished and its result kept for that half-step (or
+        for gather_factors); without one, the gather step() would issue
+        is issued here instead — never a second one. World 1: a view."""
+        if self._pending_y is not None:
+            Yfull = self._pending_y.finish()
+        else:
+            wire = (torch.bfloat16 if self.p.gather_dtype == "bf16"
+                    else None)
+            Yfull = pdist.all_gather_rows(self.Y, self.n_items,
+                                          wire_dtype=wire)
+        self._pending_y = _Gathered(Yfull)
+        return Yfull
+
+    def loss(self) -> dict:
+        """The training objective at the current factors (formulas in
+        ops/als.py): {"loss", "sq_err", "nnz"} plus "rmse" in explicit
+        mode, as Python numbers, identical on every rank.
+
+        One streaming pass over this rank's user CSR (als_residual_sums)
+        with the local X rows and the full Y — the Y the next user
+        half-step trains against, so with gather_dtype="bf16" and more
+        than one rank the loss is over the bf16-rounded Y. Each rank adds
+        its regulariser parts and local Gramians; one fp64 all-reduce of
+        the packed scalars and (implicit) one of the two f x f Gramians
+        make the result global. Collective: every rank must call it."""
+        p = self.p
+        Yfull = self._full_y()
+        Yloc = Yfull[self.i_lo:self.i_hi]
+        indptr, indices, values = self.user_csr
+        sums = als_ops.als_residual_sums(indptr, indices, values, self.X,
+                                         Yfull, p.alpha, p.implicit)
+        if p.implicit:
+            reg = (als_ops.regulariser_sum(self.X, None)
+                   + als_ops.regulariser_sum(Yloc, None))
+        else:
+            m_ptr = self.item_csr[0]
+            reg = (als_ops.regulariser_sum(self.X, indptr[1:] - indptr[:-1])
+                   + als_ops.regulariser_sum(Yloc, m_ptr[1:] - m_ptr[:-1]))
+        nnz = torch.tensor(float(indices.shape[0]), dtype=torch.float64,
+                           device=sums.device)
+        packed = pdist.all_reduce_sum(
+            torch.stack([sums[0], sums[1], reg, nnz]))
+        frob = 0.0
+        if p.implicit:
+            grams = pdist.all_reduce_sum(torch.stack(
+                [als_ops.gramian(self.X), als_ops.gramian(Yloc)]).double())
+            frob = float((grams[0] * grams[1]).sum())
+        A, B, reg, nnz = packed.tolist()
+        return als_ops.combine_objective(A, B, reg, frob, int(nnz),
+                                         p.lambda_, p.implicit)
+
+    def _record_loss(self, iteration: int) -> bool:
+        """Evaluate the objective after `iteration`, append it to
+        loss_history, log it; True when tol says to stop. The value is
+        the all-reduced one, so every rank decides alike."""
+        import logging
+        rec = {"iteration": iteration, **self.loss()}
+        prev = self.loss_history[-1]["loss"] if self.loss_history else None
+        self.loss_history.append(rec)
+        logging.getLogger(__name__).info(
+            "ALS iteration %d: loss %.9g%s", iteration, rec["loss"],
+            f" rmse {rec['rmse']:.6g}" if "rmse" in rec else "")
+        return (self.p.tol > 0 and prev is not None
+                and prev - rec["loss"] <= self.p.tol * abs(prev))
+
     # ------------------------------------------------------- checkpointing
 
     def _ckpt_path(self) -> Optional[str]:
@@ -278,12 +366,25 @@ class ALSTrainer:
         With checkpoint_every/checkpoint_dir set, local shards are
         persisted every N iterations and fit() resumes from the latest
         checkpoint after a crash (every rank must see the same
-        checkpoint_dir state)."""
+        checkpoint_dir state).
+
+        With loss_every (or tol) set, the objective is evaluated after
+        every loss_every-th iteration into self.loss_history, one
+        {"iteration": k, ...loss()} per evaluation, and tol > 0 ends the
+        training early on every rank at once. The history is not
+        checkpointed: after a resume it starts at the resumed
+        iteration."""
         start = self.load_checkpoint() if self._ckpt_path() else 0
         if self.X is None:
             self.init_factors()
+        loss_every = self.p.loss_every or (1 if self.p.tol > 0 else 0)
+        if loss_every:
+            self.loss_history = []
         for it in range(start, self.p.iterations):
             self.step()
+            if (loss_every and (it + 1) % loss_every == 0
+                    and self._record_loss(it + 1)):
+                break
             if (self.p.checkpoint_every
                     and (it + 1) % self.p.checkpoint_every == 0
                     and it + 1 < self.p.iterations):

@@ -203,6 +203,140 @@ def als_solve_ref(indptr, indices, values, Y, YtY=None, lam=0.01, alpha=1.0,
     return X
 
 
+# ------------------------------------------------------------- objective
+#
+# What the solvers above minimise, with s_ui = x_u . y_i, sums marked
+# "obs" over the stored ratings, n_u / m_i the row degrees of the user
+# and item CSR:
+#
+#   explicit (ALS-WR):  L = sum_obs (r - s)^2
+#                           + lam (sum_u n_u |x_u|^2 + sum_i m_i |y_i|^2)
+#   implicit (Hu-Koren, p = 1 and c = 1 + alpha r on stored pairs):
+#                       L = sum_obs [(1 + alpha r)(1 - s)^2 - s^2]
+#                           + <XtX, YtY>_F + lam (|X|_F^2 + |Y|_F^2)
+#
+# <XtX, YtY>_F is the sum of s^2 over ALL user-item pairs; setting the
+# gradient in x_u to zero gives the systems in als_solve's docstring.
+# The only part that touches every rating is the pair of sums
+#   A = sum_obs w (t - s)^2,  B = sum_obs s^2
+# with (w, t) = (1, r) explicit, (1 + alpha r, 1) implicit.
+
+_LOSS_CHUNK = 1 << 20  # ratings per chunk of the torch reference
+
+
+def als_residual_sums_ref(indptr, indices, values, X, Y, alpha=1.0,
+                          implicit=False, pred=None) -> torch.Tensor:
+    """[A, B] as a float64 [2] tensor in chunked torch: s in the factors'
+    dtype, everything after it in fp64. The CPU path, and what the GPU
+    kernel is validated against."""
+    nnz = indices.shape[0]
+    out = torch.zeros(2, dtype=torch.float64, device=X.device)
+    for a in range(0, nnz, _LOSS_CHUNK):
+        b = min(nnz, a + _LOSS_CHUNK)
+        pos = torch.arange(a, b, device=indptr.device)
+        rows = torch.searchsorted(indptr, pos, right=True) - 1
+        s = (X[rows] * Y[indices[a:b].long()]).sum(1)
+        if pred is not None:
+            pred[a:b] = s
+        s = s.double()
+        r = values[a:b].double()
+        if implicit:
+            out[0] += ((1.0 + float(alpha) * r) * (1.0 - s) ** 2).sum()
+        else:
+            out[0] += ((r - s) ** 2).sum()
+        out[1] += (s * s).sum()
+    return out
+
+
+def als_residual_sums(indptr: torch.Tensor, indices: torch.Tensor,
+                      values: torch.Tensor, X: torch.Tensor,
+                      Y: torch.Tensor, alpha: float = 1.0,
+                      implicit: bool = False,
+                      pred: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[A, B] = [sum w (t - s)^2, sum s^2] over the stored ratings of a
+    CSR whose rows are X's and whose columns are Y's, as a float64 [2]
+    tensor on the inputs' device.
+
+    On GPU one streaming HIP kernel (als_loss.hip) gathers the item rows
+    where they lie: any rank 1 <= f <= 128, unpadded fp32 factors, fp32
+    fma-chain dots, fp64 from there on, bit-reproducible. pred, if given
+    ([nnz] fp32), receives s per rating. On CPU: als_residual_sums_ref."""
+    if not X.is_cuda:
+        return als_residual_sums_ref(indptr, indices, values, X, Y, alpha,
+                                     implicit, pred)
+    from predictionio_amd.ops import hip_ext
+    ext = hip_ext()
+    ip, ix, vv = indptr.contiguous(), indices.contiguous(), values.contiguous()
+    # same guard as als_solve: an out-of-range id (or a row pointer past
+    # the ratings) is an out-of-bounds gather
+    if ix.numel():
+        mn, mx = int(ix.min()), int(ix.max())
+        if mx >= Y.shape[0] or mn < 0:
+            raise ValueError(
+                f"CSR column id out of range: [{mn}, {mx}]"
+                f" vs {Y.shape[0]} factor rows")
+    if ip.numel() and (int(ip[0]) < 0 or int(ip[-1]) > ix.numel()):
+        raise ValueError(
+            f"CSR row pointers [{int(ip[0])}, {int(ip[-1])}] outside the"
+            f" {ix.numel()} stored ratings")
+    # X and Y go as they are: a non-contiguous factor matrix raises in
+    # the binding; it is never copied (they are multi-GB)
+    return ext.als_residual_sums(ip, ix, vv, X, Y, float(alpha),
+                                 bool(implicit), pred)
+
+
+def sq_row_norms(F: torch.Tensor) -> torch.Tensor:
+    """|row|^2 of every row of F, computed and returned in fp64 (row
+    chunks, so a multi-GB factor matrix is never copied whole)."""
+    out = torch.empty(F.shape[0], dtype=torch.float64, device=F.device)
+    for a in range(0, F.shape[0], _LOSS_CHUNK):
+        out[a:a + _LOSS_CHUNK] = F[a:a + _LOSS_CHUNK].double().square().sum(1)
+    return out
+
+
+def regulariser_sum(F: torch.Tensor,
+                    degrees: Optional[torch.Tensor]) -> torch.Tensor:
+    """sum_rows deg |row|^2 (ALS-WR) or, with degrees None, |F|_F^2, as
+    an fp64 scalar tensor."""
+    n2 = sq_row_norms(F)
+    return n2.sum() if degrees is None else (n2 * degrees.double()).sum()
+
+
+def combine_objective(A: float, B: float, reg: float, frob: float,
+                      nnz: int, lam: float, implicit: bool) -> dict:
+    """Assemble the objective from its (globally summed) parts. sq_err is
+    A: the squared error over the stored ratings, confidence-weighted in
+    implicit mode. rmse (explicit only) is sqrt(A / nnz)."""
+    if implicit:
+        return {"loss": A - B + frob + lam * reg, "sq_err": A, "nnz": nnz}
+    return {"loss": A + lam * reg, "sq_err": A, "nnz": nnz,
+            "rmse": (A / nnz) ** 0.5 if nnz else 0.0}
+
+
+def als_objective(indptr: torch.Tensor, indices: torch.Tensor,
+                  values: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
+                  lam: float = 0.01, alpha: float = 1.0,
+                  implicit: bool = False) -> dict:
+    """The training objective the solvers minimise (formulas above) for a
+    whole user-major CSR: {"loss", "sq_err", "nnz"} plus "rmse" in
+    explicit mode, as Python numbers. The residual sums come from
+    als_residual_sums; the Gramians are gramian() in the factors' dtype;
+    their Frobenius product and the row-norm sums are fp64."""
+    sums = als_residual_sums(indptr, indices, values, X, Y, alpha, implicit)
+    if implicit:
+        reg = regulariser_sum(X, None) + regulariser_sum(Y, None)
+        frob = (gramian(X).double() * gramian(Y).double()).sum()
+    else:
+        n_u = indptr[1:] - indptr[:-1]
+        m_i = torch.bincount(indices.long(), minlength=Y.shape[0])
+        reg = regulariser_sum(X, n_u) + regulariser_sum(Y, m_i)
+        frob = torch.zeros((), dtype=torch.float64, device=X.device)
+    A, B, reg, frob = torch.stack(
+        [sums[0], sums[1], reg, frob]).tolist()
+    return combine_objective(A, B, reg, frob, int(indices.shape[0]),
+                             float(lam), implicit)
+
+
 def build_csr(rows: torch.Tensor, cols: torch.Tensor, vals: torch.Tensor,
               n_rows: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(row, col, val) triples → CSR (indptr i64, indices i32, values f32).

@@ -43,6 +43,14 @@ extern "C" void launch_topk_rescore(
     const float* Xq, const float* Y, const int* idx, float* out,
     long long B, int C, int f, hipStream_t stream);
 
+extern "C" int als_loss_grid(long long n_rows, int n_cu);
+
+extern "C" void launch_als_loss(
+    const long long* indptr, const int* indices, const float* values,
+    const float* X, const float* Y, float* pred, double* partials,
+    long long n_rows, int f, double alpha, int implicit_mode, int grid,
+    hipStream_t stream);
+
 namespace {
 
 void check_cuda_f32(const torch::Tensor& t, const char* name) {
@@ -253,6 +261,66 @@ torch::Tensor als_row_transform(torch::Tensor in, torch::Tensor W,
   return X;
 }
 
+// The two sums over stored ratings that the ALS objective needs (see
+// als_loss.hip): with s = dot(X[u], Y[indices[p]]),
+//   [A, B] = [sum w (t - s)^2, sum s^2]
+//   explicit: (w, t) = (1, r)      implicit: (w, t) = (1 + alpha r, 1)
+// as a float64 [2] device tensor; no host sync. X holds the CSR's rows,
+// Y the columns' factors; any rank 1 <= f <= 128, unpadded. pred, if
+// given, receives s per rating. Column ids are trusted (ops/als.py
+// range-checks them first).
+torch::Tensor als_residual_sums(torch::Tensor indptr, torch::Tensor indices,
+                                torch::Tensor values, torch::Tensor X,
+                                torch::Tensor Y, double alpha,
+                                bool implicit_mode,
+                                c10::optional<torch::Tensor> pred) {
+  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt64 &&
+                  indptr.is_contiguous() && indptr.dim() == 1 &&
+                  indptr.size(0) >= 1,
+              "indptr must be a contiguous 1-D i64 GPU tensor");
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+                  indices.is_contiguous() && indices.dim() == 1,
+              "indices must be a contiguous 1-D i32 GPU tensor");
+  check_cuda_f32(values, "values");
+  check_cuda_f32(X, "X");
+  check_cuda_f32(Y, "Y");
+  TORCH_CHECK(values.dim() == 1 && X.dim() == 2 && Y.dim() == 2,
+              "values must be 1-D, X and Y 2-D");
+  TORCH_CHECK(indices.device() == X.device() && indptr.device() == X.device() &&
+                  values.device() == X.device() && Y.device() == X.device(),
+              "all tensors must be on one device");
+  const int64_t n_rows = indptr.size(0) - 1;
+  const int64_t nnz = indices.size(0);
+  const int64_t f = X.size(1);
+  TORCH_CHECK(X.size(0) == n_rows, "X must have one row per CSR row");
+  TORCH_CHECK(Y.size(1) == f, "X/Y rank mismatch");
+  TORCH_CHECK(f >= 1 && f <= 128, "rank must be in [1, 128], got ", f);
+  TORCH_CHECK(values.size(0) == nnz, "indices/values mismatch");
+  float* pred_ptr = nullptr;
+  if (pred.has_value()) {
+    check_cuda_f32(*pred, "pred");
+    TORCH_CHECK(pred->dim() == 1 && pred->size(0) == nnz &&
+                    pred->device() == X.device(),
+                "pred must be [nnz] on X's device");
+    pred_ptr = pred->data_ptr<float>();
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  const auto f64 = X.options().dtype(torch::kFloat64);
+  if (n_rows == 0 || nnz == 0) return torch::zeros({2}, f64);
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const int n_cu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const int grid = als_loss_grid((long long)n_rows, n_cu);
+  auto partials = torch::empty({grid, 2}, f64);  // every block writes its row
+  launch_als_loss(
+      reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
+      indices.data_ptr<int>(), values.data_ptr<float>(), X.data_ptr<float>(),
+      Y.data_ptr<float>(), pred_ptr, partials.data_ptr<double>(),
+      (long long)n_rows, (int)f, alpha, implicit_mode ? 1 : 0, grid, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return partials.sum(0);
+}
+
 // Fused masked top-K scoring: per-slice candidate groups; caller merges
 // with a small torch.topk. Returns (vals [B, n_slices*4*K], idx i32).
 std::tuple<torch::Tensor, torch::Tensor> topk_score(
@@ -410,6 +478,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("als_row_transform", &als_row_transform,
         "out[N, f] = in[N, f] . W[f, f], fp32 MFMA row transform",
         py::arg("in_"), py::arg("W"), py::arg("out") = py::none());
+  m.def("als_residual_sums", &als_residual_sums,
+        "[sum w (t - s)^2, sum s^2] over the stored ratings, float64",
+        py::arg("indptr"), py::arg("indices"), py::arg("values"),
+        py::arg("X"), py::arg("Y"), py::arg("alpha") = 1.0,
+        py::arg("implicit_mode") = false, py::arg("pred") = py::none());
   m.def("topk_score", &topk_score, "Fused masked top-K scoring",
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),

@@ -242,7 +242,8 @@ class ALSModel(PersistentModel):
 
 class ALSAlgorithm(Algorithm):
     """Params: rank, numIterations, lambda, [alpha], [implicitPrefs],
-    [seed] (engine.json `als` params in the reference template)."""
+    [seed] (engine.json `als` params in the reference template), plus
+    [lossEvery] and [convergenceTol] (ALSParams.loss_every / tol)."""
 
     def train(self, pd: PreparedData) -> ALSModel:
         if pd.columns is not None and len(pd.columns):
@@ -288,7 +289,11 @@ class ALSAlgorithm(Algorithm):
             # reference checkpoints ALS every 10 iterations
             # (ALSAlgorithm.scala:85); here it is crash-resume
             checkpoint_every=int(self.params.get("checkpointEvery", 0)),
-            checkpoint_dir=self.params.get("checkpointDir"))
+            checkpoint_dir=self.params.get("checkpointDir"),
+            # optional: log the training objective every N iterations,
+            # stop early once it improves by no more than the tolerance
+            loss_every=int(self.params.get("lossEvery", 0)),
+            tol=float(self.params.get("convergenceTol", 0.0)))
         device = pdist.compute_device()
         X, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)

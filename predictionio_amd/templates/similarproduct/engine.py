@@ -179,7 +179,8 @@ class SimilarModel:
 
 
 class ALSAlgorithm(Algorithm):
-    """Params: rank, numIterations, lambda, alpha, [seed]."""
+    """Params: rank, numIterations, lambda, alpha, [seed], [lossEvery],
+    [convergenceTol]."""
 
     def train(self, pd: PreparedData) -> SimilarModel:
         if not pd.view_events:
@@ -204,7 +205,9 @@ class ALSAlgorithm(Algorithm):
             iterations=int(self.params.get("numIterations", 20)),
             lambda_=float(self.params.get("lambda", 0.01)),
             alpha=float(self.params.get("alpha", 1.0)),
-            implicit=True, seed=self.params.get("seed"))
+            implicit=True, seed=self.params.get("seed"),
+            loss_every=int(self.params.get("lossEvery", 0)),
+            tol=float(self.params.get("convergenceTol", 0.0)))
         device = pdist.compute_device()
         _, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)
