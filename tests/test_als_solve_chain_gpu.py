@@ -8,62 +8,23 @@ recipe of test_woodbury_seam: Y = randn / sqrt(f), values in [0.5, 3.5),
 lam = 0.05, alpha = 2.0, 400 columns.
 """
 
-import functools
-import math
-
 import pytest
 import torch
+
+from _als_solve_oracle import (
+    ALPHA, LAM, TOL, _csr, _factors, _ref64, _rel_fro, degenerate_problem,
+    every_degree_problem,
+)
 
 pytestmark = pytest.mark.gpu
 
 requires_gpu = pytest.mark.skipif(not torch.cuda.is_available(),
                                   reason="needs MI355X")
 
-N_COLS = 400
-LAM, ALPHA = 0.05, 2.0
-TOL = 3e-3  # the seam test's tolerance
-
-# one row of every degree 0..40 (all three Woodbury variants, both sides
-# of each variant boundary, the first dense rows) plus the dense kernel
-# around its 64-lane width and one long row
-DEGREES = list(range(41)) + [63, 64, 65, 100]
-
 # Relative Frobenius error of the parent commit (shfl pivots, IEEE
 # divisions) against the float64 reference on every_degree_problem(64, .),
 # measured once on an MI355X; see the NOTES.md perf ledger.
 PARENT_REL_FRO = {True: 5.246e-07, False: 2.402e-07}
-
-
-def _csr(sizes, g, cols_of=None, vals_of=None):
-    """CSR with sizes[r] entries in row r: random columns and values in
-    [0.5, 3.5) unless cols_of / vals_of (row -> tensor) override them."""
-    cols, vals = [], []
-    for r, n in enumerate(sizes):
-        c = torch.randint(0, N_COLS, (n,), generator=g)
-        v = torch.rand(n, generator=g) * 3 + 0.5
-        if cols_of is not None and r in cols_of:
-            c = cols_of[r]
-        if vals_of is not None and r in vals_of:
-            v = vals_of[r]
-        cols.append(c)
-        vals.append(v)
-    indptr = torch.tensor([0] + torch.tensor(sizes).cumsum(0).tolist(),
-                          dtype=torch.int64)
-    return (indptr, torch.cat(cols).to(torch.int32),
-            torch.cat(vals).float())
-
-
-def _factors(f, g):
-    return (torch.randn((N_COLS, f), generator=g) / math.sqrt(f)).float()
-
-
-def _ref64(indptr, cols, vals, Y, lam, implicit):
-    from predictionio_amd.ops import als as als_ops
-    Yd = Y.double()
-    return als_ops.als_solve_ref(
-        indptr, cols, vals.double(), Yd,
-        YtY=als_ops.gramian(Yd) if implicit else None,
-        lam=lam, alpha=ALPHA, implicit=implicit)
 
 
 def _solve_gpu(indptr, cols, vals, Y, lam, implicit, **kw):
@@ -73,32 +34,11 @@ def _solve_gpu(indptr, cols, vals, Y, lam, implicit, **kw):
                              implicit=implicit, **kw)
 
 
-@functools.lru_cache(maxsize=None)
-def every_degree_problem(f, implicit):
-    """DEGREES laid out twice in one CSR, ascending and then in a seeded
-    shuffle: adjacent rows are the two waves of one workgroup, so they
-    carry different degrees and (at the boundaries and throughout the
-    shuffle) different kernel variants. Returns the problem and its
-    float64 reference, computed once and shared."""
-    g = torch.Generator().manual_seed(1234 + f)
-    perm = torch.randperm(len(DEGREES), generator=g).tolist()
-    sizes = DEGREES + [DEGREES[i] for i in perm]
-    assert all(a != b for a, b in zip(sizes[::2], sizes[1::2]))
-    indptr, cols, vals = _csr(sizes, g)
-    Y = _factors(f, g)
-    X64 = _ref64(indptr, cols, vals, Y, LAM, implicit)
-    return sizes, indptr, cols, vals, Y, X64
-
-
 def _solve_every_degree(f, implicit):
     sizes, indptr, cols, vals, Y, X64 = every_degree_problem(f, implicit)
     out = torch.full((len(sizes), f), float("nan"), device="cuda")
     X = _solve_gpu(indptr, cols, vals, Y, LAM, implicit, out=out).cpu()
     return sizes, X, X64
-
-
-def _rel_fro(X, X64):
-    return ((X.double() - X64).norm() / X64.norm()).item()
 
 
 @requires_gpu
@@ -169,19 +109,8 @@ def test_degenerate_pivots():
       (2.0e-3); the test re-checks that on the CPU first.
     """
     from predictionio_amd.ops import als as als_ops
-    g = torch.Generator().manual_seed(555)
-    zero_deg = [1, 20, 24, 32, 40]
-    rep_deg = [2, 20, 32, 40]
-    sizes = zero_deg + [0] + rep_deg + [0]
-    rep_rows = {len(zero_deg) + 1 + i: n for i, n in enumerate(rep_deg)}
-    cols_of = {r: torch.full((n,), 7 + r) for r, n in rep_rows.items()}
-    vals_of = {r: torch.zeros(n) for r, n in enumerate(zero_deg)}
-    Y = _factors(64, g)
     for implicit in (True, False):
-        gi = torch.Generator().manual_seed(556)
-        # all-zero values only in implicit mode; explicit keeps random ones
-        indptr, cols, vals = _csr(sizes, gi, cols_of,
-                                  vals_of if implicit else None)
+        sizes, indptr, cols, vals, Y = degenerate_problem(implicit)
         X64 = _ref64(indptr, cols, vals, Y, LAM, implicit)
         out = torch.full((len(sizes), 64), float("nan"), device="cuda")
         X = _solve_gpu(indptr, cols, vals, Y, LAM, implicit, out=out).cpu()
