@@ -59,6 +59,24 @@ __device__ __forceinline__ float lane_bcast(float v, int k) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
 }
 
+// 64-row block scan of the one-wave-per-row solvers: lane l forms the
+// degree of row base + l from two coalesced indptr loads and a ballot
+// marks the rows whose degree lies in (lo, hi] — the rows this kernel
+// owns. The wave then walks the set bits. One row per trip cost a
+// dependent scalar load per row, skipped rows included, and a half-step
+// runs several such kernels over all of its rows. Both indices are
+// clamped to n_rows: indptr has n_rows + 1 entries. The result is
+// wave-uniform (an SGPR pair).
+__device__ __forceinline__ unsigned long long owned_rows_mask(
+    const long long* __restrict__ indptr, long long base, int n_rows,
+    int lane, int lo, int hi) {
+  const long long r = base + lane;
+  const long long r0 = r < n_rows ? r : n_rows;
+  const long long r1 = r + 1 < n_rows ? r + 1 : n_rows;
+  const int deg = (int)(indptr[r1] - indptr[r0]);
+  return __builtin_amdgcn_ballot_w64(r < n_rows && deg > lo && deg <= hi);
+}
+
 
 template <int F>
 __global__ __launch_bounds__(256) void als_solve_kernel(
@@ -425,12 +443,18 @@ void als_solve_wave_kernel(
   __shared__ unsigned short ysT[2][BF16G ? F : 1][BF16G ? TP : 1];
   __shared__ float Lc[2][F][LP];       // persisted L columns: Lc[w][k][j] = L[j][k]
 
-  for (long long row = (long long)blockIdx.x * 2 + wave; row < n_rows;
-       row += (long long)gridDim.x * 2) {
+  // blocks of 64 consecutive rows per wave; rows outside
+  // (skip_below, skip_above] belong to the Woodbury / workgroup kernels
+  // and cost nothing beyond the block's two coalesced loads
+  for (long long base = ((long long)blockIdx.x * 2 + wave) * 64;
+       base < n_rows; base += (long long)gridDim.x * 128) {
+    unsigned long long todo =
+        owned_rows_mask(indptr, base, n_rows, lane, skip_below, skip_above);
+  while (todo != 0) {
+    const long long row = base + __builtin_ctzll(todo);
+    todo &= todo - 1;
     const long long start = uniform_i64(indptr[row]);
     const int nnz = uniform_i32((int)(indptr[row + 1] - start));
-    if (nnz <= skip_below || nnz > skip_above)
-      continue;  // Woodbury / workgroup kernels own these rows
 
     // ln == lane, but tied to this row's start so the per-k lane compares
     // of the solve are formed where they are used: hoisted out of the row
@@ -678,11 +702,12 @@ void als_solve_wave_kernel(
     }
 
     if (lane < F) X[row * (long long)F + lane] = b_reg;
+  }  // owned rows of the block
   }
 }
 
 // ---------------------------------------------------------------------------
-// Woodbury solver — rows with nnz <= WOODBURY_MAX_NNZ (the common case for
+// Woodbury solver — rows with nnz <= woodbury_max_nnz() (the common case for
 // recommendation data: the bench config has nnz/row = 20, rank = 64).
 //
 // Instead of building + factorizing the FxF normal matrix per row, exploit
@@ -704,13 +729,11 @@ void als_solve_wave_kernel(
 //
 // Cost per row: n^2/2 F MACs for G + n^3/3 solve — ~5x fewer FLOPs than
 // the FxF Cholesky at n=20, F=64, with NO long serial dependency chains.
-// One wave per row, 2 waves per workgroup; rows with nnz > WOODBURY_MAX_NNZ
+// One wave per row, 2 waves per workgroup; rows with nnz > woodbury_max_nnz()
 // are skipped here and handled by the wave/workgroup kernels.
 // LDS rows padded to F+4 floats so G-dot reads from row i (stride 68) land
 // in different bank groups per lane.
 // ---------------------------------------------------------------------------
-
-#define WOODBURY_MAX_NNZ 32
 
 
 // Two NW instantiations: rows with nnz <= 24 run the NW=24 variant whose
@@ -724,8 +747,27 @@ void als_solve_wave_kernel(
 // numerics study (profiles/bf16_numerics_study.txt) bounds the staged-
 // factor rounding at ~1e-5 relative ALS objective. Opt-in via
 // PIO_ALS_STAGE_BF16=1 (the V pointer then carries bf16 data).
+//
+// The wide instantiations NW = 40 and 48 (F >= 64, fp32 staging) take the
+// rows just above 32 off the dense kernels: the push-through identity
+// holds for any n, and at n = 40, F = 64 it is ~72 K MACs on a 40-step
+// chain against ~169 K on a 64-step one. LDS caps them at 4 (NW = 40),
+// 3 (NW = 48) and, at F = 128, 2 workgroups per CU, so they are compiled
+// for 2 waves per SIMD: the register cap stays at the LDS cap.
+constexpr int woodbury_min_waves(int nw) {
+  return nw > 32 ? 2 : (nw > 24 ? 5 : 6);
+}
+// G build of the wide instantiations: 16x16 f32-MFMA blocks, or (built
+// with -DPIO_ALS_WIDE_G_VALU, for A/B runs) the VALU pair loop
+#ifdef PIO_ALS_WIDE_G_VALU
+constexpr bool WIDE_G_ON_MFMA = false;
+#else
+constexpr bool WIDE_G_ON_MFMA = true;
+#endif
+
 template <int F, int NW, int NLO, bool BF16S = false>
-__global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
+__global__ __launch_bounds__(128, woodbury_min_waves(NW))
+void als_woodbury_kernel(
     const long long* __restrict__ indptr,
     const int* __restrict__ indices,
     const float* __restrict__ values,
@@ -761,11 +803,20 @@ __global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
   const float* src = implicit_mode ? V : Y;
   const unsigned short* srch = reinterpret_cast<const unsigned short*>(V);
 
-  for (long long row = (long long)blockIdx.x * 2 + wave; row < n_rows;
-       row += (long long)gridDim.x * 2) {
+  // blocks of 64 consecutive rows per wave; rows of another variant or of
+  // the dense kernel (n <= NLO or n > NW) are never visited
+  for (long long base = ((long long)blockIdx.x * 2 + wave) * 64;
+       base < n_rows; base += (long long)gridDim.x * 128) {
+    unsigned long long todo =
+        owned_rows_mask(indptr, base, n_rows, lane, NLO, NW);
+  while (todo != 0) {
+    const long long row = base + __builtin_ctzll(todo);
+    todo &= todo - 1;
     const long long start = uniform_i64(indptr[row]);
     const int n = uniform_i32((int)(indptr[row + 1] - start));
-    if (n > NW || n <= NLO) continue;  // other variant / dense kernel
+    // never taken (the ballot admitted the row); it tells the compiler
+    // NLO < n <= NW, which folds the solve's `k < n` guards at k <= NLO
+    if (n > NW || n <= NLO) continue;
     if (n == 0 && NLO < 0) {
       for (int e = lane; e < F; e += 64)
         X[row * (long long)F + e] = 0.f;
@@ -825,8 +876,84 @@ __global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
     // 6.1 vs 5.9 ms per 2M rows): its G phase shrank 3x but the other
     // waves' M-solves, which live on v_pk_fma_f32, slowed by as much
     // while the matrix pipe was busy.
-    constexpr bool MFMA_G = !BF16S && NW >= 24;
-    if constexpr (MFMA_G) {
+    // NW > 32 does not fit one 32x32 tile: 16x16 blocks (below).
+    constexpr bool MFMA_G = !BF16S && NW >= 24 && NW <= 32;
+    constexpr bool MFMA_G16 = !BF16S && NW > 32 && WIDE_G_ON_MFMA;
+    if constexpr (MFMA_G16) {
+      // G as 3 x 3 blocks of 16 on v_mfma_f32_16x16x4_f32, the 6 blocks on
+      // or below the diagonal only: 6 F/4 MFMAs of 32 cycles (3072 matrix
+      // cycles per row at F = 64; three 32x32x2 tiles would take 6144).
+      // Lane l holds A[l&15][k = l>>4] = B[k][l&15], so for V.V^T the A
+      // operand of block row bi and the B operand of block column bj are
+      // the lanes' own rows 16 bi + (l&15) and 16 bj + (l&15). As in the
+      // 32x32 build the k order is free: lane l reads the b128 quad at
+      // k = 16 q + 4 (l>>4) of each of its 3 rows and feeds element t of
+      // every quad to MFMA t — 3 F/16 ds_read_b128 per row, every staged
+      // element read once. Lanes whose row is >= NW read row NW - 1.
+      // Rows >= n are stale and only reach entries with i >= n or j >= n.
+      static_assert(NW % 4 == 0 && NW <= 48 && F % 16 == 0,
+                    "3 x 3 blocks of 16, whole quads");
+      const int gr = lane & 15, gk = lane >> 4;
+      const f32x4_t* vq[3];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const int r = 16 * b + gr;
+        vq[b] = reinterpret_cast<const f32x4_t*>(
+            &yl[(r < NW ? r : NW - 1) * FP + 4 * gk]);
+      }
+      f32x4_t acc[6];   // block (bi, bj), bj <= bi, at bi (bi + 1) / 2 + bj
+#pragma unroll
+      for (int p = 0; p < 6; ++p) acc[p] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < F / 16; ++q) {
+        f32x4_t a[3];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) a[b] = vq[b][4 * q];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int bi = 0; bi < 3; ++bi)
+#pragma unroll
+            for (int bj = 0; bj <= bi; ++bj)
+              acc[bi * (bi + 1) / 2 + bj] =
+                  __builtin_amdgcn_mfma_f32_16x16x4f32(
+                      a[bi][t], a[bj][t], acc[bi * (bi + 1) / 2 + bj],
+                      0, 0, 0);
+      }
+      // C/D layout: col = lane&15, row = 4 (lane>>4) + reg, so block
+      // (bi, bj) leaves G[R0 + t][C] in the lane, R0 = 16 bi + 4 gk,
+      // C = 16 bj + gr. By symmetry that is the contiguous quad
+      // M[C][R0 .. R0+3] — one ds_write_b128, which is all a diagonal
+      // block needs; an off-diagonal block is mirrored into M[R0 + t][C]
+      // with four ds_write_b32. Stores only where C < NW and R0 < NW
+      // (NW % 4 == 0, so the quad ends inside the row), dv reads likewise.
+      const float dg = implicit_mode ? 1.f : reg;
+#pragma unroll
+      for (int bi = 0; bi < 3; ++bi) {
+        const int R0 = 16 * bi + 4 * gk;
+        f32x4_t dr = {1.f, 1.f, 1.f, 1.f};
+        if (implicit_mode && R0 < NW)
+          dr = *reinterpret_cast<const f32x4_t*>(&dv[wave][R0]);
+#pragma unroll
+        for (int bj = 0; bj <= bi; ++bj) {
+          const int C = 16 * bj + gr;
+          if (R0 < NW && C < NW) {
+            const float dc = implicit_mode ? dv[wave][C] : 1.f;
+            f32x4_t m4;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              m4[t] = acc[bi * (bi + 1) / 2 + bj][t] * (dr[t] * dc);
+              if (bi == bj) m4[t] += (R0 + t == C) ? dg : 0.f;
+            }
+            *reinterpret_cast<f32x4_t*>(&M[wave][C][R0]) = m4;
+            if (bi != bj) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) M[wave][R0 + t][C] = m4[t];
+            }
+          }
+        }
+      }
+    } else if constexpr (MFMA_G) {
       // fp32 staging: G = V_u . V_u^T as ONE 32x32 tile on the f32 matrix
       // pipe (v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate, a k-ordered
       // fmaf chain). For V.V^T the A and B fragments are the same register
@@ -1073,6 +1200,7 @@ __global__ __launch_bounds__(128, NW > 24 ? 5 : 6) void als_woodbury_kernel(
       atomicAdd(&prof[4], 1ull);        // samples
     }
     wave_sync();
+  }  // owned rows of the block
   }
 }
 
@@ -1347,6 +1475,43 @@ __global__ __launch_bounds__(128, 3) void als_woodbury2_kernel(
 // launcher
 // ---------------------------------------------------------------------------
 
+// Largest degree the Woodbury pass takes; the dense kernels skip rows up to
+// it. 48 where the wide instantiations exist and apply (f in {64, 128},
+// fp32 staging, single-row kernels), 32 otherwise: where one of the opt-in
+// switches (PIO_ALS_DUAL, PIO_ALS_STAGE_BF16, PIO_ALS_MFMA_GRAMIAN) selects
+// a kernel, the routing is what it was before the wide variants; where the
+// launcher ignores a switch (bf16 staging in explicit mode, the MFMA
+// Gramian at f != 64) the result stays the default route's, bit for bit.
+// PIO_ALS_WOODBURY_MAX=32 keeps rows 33..48 on the dense kernels (A/B runs
+// and tests of both routes in one build). `opt_in` must depend on the
+// environment, f and implicit_mode alone — not on V or `which` — so that
+// every phase of an implicit solve (Woodbury pass, dense pass) sees the
+// same bound.
+static int woodbury_max_nnz(int f, bool opt_in) {
+  if ((f != 64 && f != 128) || opt_in) return 32;
+  const char* e = getenv("PIO_ALS_WOODBURY_MAX");
+  if (e != nullptr && e[0] == '3' && e[1] == '2' && e[2] == '\0') return 32;
+  return 48;
+}
+
+// instantiation guard: the wide Woodbury variants exist only at F >= 64
+template <int FF>
+static void launch_woodbury_wide(int grid_w, hipStream_t stream,
+    const long long* indptr, const int* indices, const float* values,
+    const float* Y, const float* V, float* X, int n_rows, float lambda,
+    float alpha, int implicit_mode, int wr_scale, unsigned long long* prof) {
+  if constexpr (FF >= 64) {
+    hipLaunchKernelGGL((als_woodbury_kernel<FF, 40, 32>), dim3(grid_w),
+                       dim3(128), 0, stream, indptr, indices, values, Y, V,
+                       X, n_rows, lambda, alpha, implicit_mode, wr_scale,
+                       prof);
+    hipLaunchKernelGGL((als_woodbury_kernel<FF, 48, 40>), dim3(grid_w),
+                       dim3(128), 0, stream, indptr, indices, values, Y, V,
+                       X, n_rows, lambda, alpha, implicit_mode, wr_scale,
+                       prof);
+  }
+}
+
 // instantiation guard: the MFMA-Gramian wave kernel exists only at F=64
 template <int FF>
 static void launch_wave_bf16g(int grid_w, hipStream_t stream,
@@ -1375,13 +1540,13 @@ extern "C" void launch_als_solve(
   //        2 = dense only, skipping Woodbury-owned rows (implicit: fills
   //            the big rows with direct X after the trsm).
   if (n_rows <= 0) return;
-  // wave/woodbury kernels: 2 rows per 128-thread workgroup
-  long long wg = ((long long)n_rows + 1) / 2;
+  // wave/woodbury kernels: one 64-row block per wave per trip, 2 waves
+  // per 128-thread workgroup
+  long long wg = ((long long)n_rows + 127) / 128;
   int grid_w = (int)(wg < (1 << 20) ? wg : (1 << 20));
   int grid_b = n_rows < (1 << 20) ? n_rows : (1 << 20);
   const bool woodbury = which != 2 &&
       (implicit_mode ? V != nullptr : true);
-  const int skip = (woodbury || which == 2) ? WOODBURY_MAX_NNZ : -1;
   const bool dense = which != 1;
   // PIO_ALS_DENSE_SPLIT=N routes rows with nnz > N to the
   // workgroup-per-row kernel (256 threads/row — 4x the per-row
@@ -1428,6 +1593,10 @@ extern "C" void launch_als_solve(
   // ride along with the beneficial PIO_ALS_STAGE_BF16 combo
   const char* e_mg = getenv("PIO_ALS_MFMA_GRAMIAN");
   const bool use_bf16s_g = e_mg != nullptr && e_mg[0] == '1';
+  const int wmax = woodbury_max_nnz(
+      f, use_dual || (stage_bf16 && implicit_mode) ||
+             (use_bf16s_g && f == 64));
+  const int skip = (woodbury || which == 2) ? wmax : -1;
   long long wg4 = ((long long)n_rows + 3) / 4;
   int grid_w2 = (int)(wg4 < (1 << 20) ? wg4 : (1 << 20));
 #define LAUNCH_WOODBURY(FF)                                                  \
@@ -1486,6 +1655,10 @@ extern "C" void launch_als_solve(
                        dim3(128), 0, stream, indptr, indices, values, Y, V,  \
                        X, n_rows, lambda, alpha, implicit_mode, wr_scale,    \
                        prof);                                                \
+    if (wmax > 32)                                                           \
+      launch_woodbury_wide<FF>(grid_w, stream, indptr, indices, values, Y,   \
+                               V, X, n_rows, lambda, alpha, implicit_mode,   \
+                               wr_scale, prof);                              \
   }
   switch (f) {
     case 16: LAUNCH_WOODBURY(16); LAUNCH_WAVE(16); break;

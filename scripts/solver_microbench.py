@@ -45,11 +45,26 @@ def bench(n_rows, n_cols, f, nnz_per_row, implicit=True, iters=10):
 
 
 if __name__ == "__main__":
-    n_rows = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("rows", nargs="?", type=int, default=2_000_000)
+    ap.add_argument("--nnz", type=int, nargs="+", default=None,
+                    help="degrees to time, e.g. 20 24 32 36 40 44 48 "
+                         "(default: 5 20 40, then the dense 100 200 at f=64)")
+    ap.add_argument("--f", type=int, nargs="+", default=[64, 128])
+    ap.add_argument("--explicit", action="store_true")
+    ap.add_argument("--iters", type=int, default=10)
+    a = ap.parse_args()
     n_cols = 1_000_000
-    for f in (64, 128):
-        for nnz_per_row in (5, 20, 40):
-            bench(n_rows, n_cols, f, nnz_per_row)
-    # the 8-GPU item-side shape: rows densify with world size
-    for nnz_per_row in (100, 200):
-        bench(n_rows // 4, n_cols, 64, nnz_per_row)
+    # the launcher reads the routing switches on every call
+    print("PIO_ALS_WOODBURY_MAX=" +
+          os.environ.get("PIO_ALS_WOODBURY_MAX", "(unset: rows up to 48 on "
+                         "the Woodbury kernels at f = 64 / 128)"), flush=True)
+    for f in a.f:
+        for nnz_per_row in (a.nnz or (5, 20, 40)):
+            bench(a.rows, n_cols, f, nnz_per_row, implicit=not a.explicit,
+                  iters=a.iters)
+    if a.nnz is None and not a.explicit:
+        # the 8-GPU item-side shape: rows densify with world size
+        for nnz_per_row in (100, 200):
+            bench(a.rows // 4, n_cols, 64, nnz_per_row, iters=a.iters)
