@@ -16,7 +16,8 @@ OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(OPS_DIR, "csrc")
 SO_PATH = os.path.join(OPS_DIR, "_pio_hip.so")
 SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
-           "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip"]
+           "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
+           "cooc_topn.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

@@ -51,6 +51,14 @@ extern "C" void launch_als_loss(
     long long n_rows, int f, double alpha, int implicit_mode, int grid,
     hipStream_t stream);
 
+extern "C" void launch_cooc_topn(
+    const long long* u_indptr, const int* u_items, const long long* i_indptr,
+    const int* i_users, const int* rows, int n_rows, int n, int tier,
+    int* pool, long long n_items, int* top_ids, int* top_cnt, int grid,
+    hipStream_t stream);
+
+extern "C" int cooc_dense_lds_max();
+
 namespace {
 
 void check_cuda_f32(const torch::Tensor& t, const char* name) {
@@ -464,6 +472,85 @@ torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
   return out;
 }
 
+// One tier of co-occurrence top-N (see cooc_topn.hip): the item rows
+// listed in `rows` are counted, selected and written to top_ids/top_cnt
+// [N, n] in place; rows not listed are left alone. tier 0 / 1: the
+// 1024- / 8192-slot LDS hash tables; tier 2: dense counters in `pool`,
+// a zero [G, N] i32 tensor that is all zero again afterwards, one
+// persistent workgroup per counter row; tier 3: dense counters in LDS,
+// N <= cooc_dense_lds_max(). Ids are trusted
+// (ops/cooccurrence.py range-checks both CSRs first).
+void cooc_topn(torch::Tensor u_indptr, torch::Tensor u_items,
+               torch::Tensor i_indptr, torch::Tensor i_users,
+               torch::Tensor rows, int64_t n, int64_t tier,
+               c10::optional<torch::Tensor> pool, torch::Tensor top_ids,
+               torch::Tensor top_cnt) {
+  auto check = [](const torch::Tensor& t, torch::ScalarType st, int64_t dim,
+                  const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st &&
+                    t.dim() == dim,
+                name, " must be a contiguous ", dim, "-D ",
+                st == torch::kInt64 ? "i64" : "i32", " GPU tensor");
+  };
+  check(u_indptr, torch::kInt64, 1, "u_indptr");
+  check(i_indptr, torch::kInt64, 1, "i_indptr");
+  check(u_items, torch::kInt32, 1, "u_items");
+  check(i_users, torch::kInt32, 1, "i_users");
+  check(rows, torch::kInt32, 1, "rows");
+  check(top_ids, torch::kInt32, 2, "top_ids");
+  check(top_cnt, torch::kInt32, 2, "top_cnt");
+  TORCH_CHECK(u_indptr.size(0) >= 1 && i_indptr.size(0) >= 1,
+              "indptr tensors must not be empty");
+  TORCH_CHECK(u_items.size(0) == i_users.size(0),
+              "the two CSRs must hold the same pairs");
+  TORCH_CHECK(n >= 1 && n <= 64, "n must be in [1, 64], got ", n);
+  TORCH_CHECK(tier >= 0 && tier <= 3, "tier must be 0, 1, 2 or 3");
+  const int64_t N = i_indptr.size(0) - 1;
+  TORCH_CHECK(N < (1LL << 31) && u_indptr.size(0) - 1 < (1LL << 31),
+              "item and user counts must be below 2^31");
+  TORCH_CHECK(top_ids.size(0) == N && top_ids.size(1) == n &&
+                  top_cnt.size(0) == N && top_cnt.size(1) == n,
+              "top_ids and top_cnt must be [N, n]");
+  const auto dev = u_indptr.device();
+  TORCH_CHECK(u_items.device() == dev && i_indptr.device() == dev &&
+                  i_users.device() == dev && rows.device() == dev &&
+                  top_ids.device() == dev && top_cnt.device() == dev,
+              "all tensors must be on one device");
+  const int64_t n_rows = rows.size(0);
+  TORCH_CHECK(n_rows < (1LL << 31), "too many rows for one launch");
+  if (n_rows == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const int n_cu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  int64_t grid;
+  int* pool_ptr = nullptr;
+  if (tier == 2) {
+    TORCH_CHECK(pool.has_value(), "the dense tier needs a counter pool");
+    check(*pool, torch::kInt32, 2, "pool");
+    TORCH_CHECK(pool->device() == dev && pool->size(0) >= 1 &&
+                    pool->size(1) == N,
+                "pool must be [G >= 1, N] on the inputs' device");
+    grid = std::min<int64_t>(pool->size(0), n_rows);
+    pool_ptr = pool->data_ptr<int>();
+  } else if (tier == 3) {
+    TORCH_CHECK(N <= cooc_dense_lds_max(), "the LDS dense tier holds at most ",
+                cooc_dense_lds_max(), " items, got ", N);
+    grid = std::min<int64_t>(n_rows, n_cu);  // 120 KB of LDS: one per CU
+  } else {
+    // LDS admits ten 16 KB / two 72 KB workgroups per CU
+    grid = std::min<int64_t>(n_rows, (int64_t)n_cu * (tier == 0 ? 8 : 2));
+  }
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_cooc_topn(
+      reinterpret_cast<const long long*>(u_indptr.data_ptr<int64_t>()),
+      u_items.data_ptr<int>(),
+      reinterpret_cast<const long long*>(i_indptr.data_ptr<int64_t>()),
+      i_users.data_ptr<int>(), rows.data_ptr<int>(), (int)n_rows, (int)n,
+      (int)tier, pool_ptr, (long long)N, top_ids.data_ptr<int>(),
+      top_cnt.data_ptr<int>(), (int)grid, stream);
+  C10_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -500,4 +587,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_rescore", &topk_rescore,
         "Exact fp32 dots of each query with its shortlisted items",
         py::arg("Xq"), py::arg("Y"), py::arg("idx"));
+  m.def("cooc_topn", &cooc_topn,
+        "Co-occurrence top-N of the listed item rows, one tier",
+        py::arg("u_indptr"), py::arg("u_items"), py::arg("i_indptr"),
+        py::arg("i_users"), py::arg("rows"), py::arg("n"), py::arg("tier"),
+        py::arg("pool"), py::arg("top_ids"), py::arg("top_cnt"));
+  m.def("cooc_dense_lds_max", &cooc_dense_lds_max,
+        "Largest item count of the LDS dense tier");
 }

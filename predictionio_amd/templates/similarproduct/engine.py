@@ -22,7 +22,6 @@ top-K kernel launch.
 
 from __future__ import annotations
 
-import warnings
 from collections import defaultdict
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Set, Tuple
@@ -329,8 +328,12 @@ class ALSAlgorithm(Algorithm):
 
 class CooccurrenceModel:
     def __init__(self, top_n: Dict[int, List[Tuple[int, int]]],
-                 item_map: BiMap, items: Dict[str, Item]):
+                 item_map: BiMap, items: Dict[str, Item],
+                 top_ids=None, top_cnt=None):
         self.top_n = top_n          # item → [(other_item, count)]
+        # the same lists as host numpy int32 [N, n]: id -1 / count 0 pad
+        self.top_ids = top_ids
+        self.top_cnt = top_cnt
         self.item_map = item_map
         self.items = items
         self.item_inv = item_map.inverse_array()
@@ -341,13 +344,13 @@ class CooccurrenceAlgorithm(Algorithm):
     (CooccurrenceAlgorithm.scala:49-108)."""
 
     def train(self, pd: PreparedData) -> CooccurrenceModel:
-        """Pair counting as ONE sparse Gramian: C = A^T A with A the
-        user×item view-incidence matrix (user-distinct), then a
-        vectorized per-item top-N — replaces the reference's self-join
-        + groupBy (CooccurrenceAlgorithm.scala:55-108) and round 1's
-        Python pair loops (quadratic in per-user views). Runs on the
-        GPU when available (torch sparse mm)."""
-        import numpy as np
+        """Pair counting as a per-item top-N over c[i][j] = number of
+        users who viewed both (user-distinct) — replaces the reference's
+        self-join + groupBy (CooccurrenceAlgorithm.scala:55-108). On a
+        GPU the fused pair-count kernels (ops/cooccurrence.py) count each
+        item row on chip and only the [N, n] result reaches the host; on
+        CPU the same op runs its sparse A^T A reference."""
+        from predictionio_amd.ops.cooccurrence import cooccurrence_topn
         item_map = BiMap.string_int(
             [v.item for v in pd.view_events] + list(pd.items))
         user_map = BiMap.string_int(v.user for v in pd.view_events)
@@ -356,40 +359,22 @@ class CooccurrenceAlgorithm(Algorithm):
         n_users = len(user_map)
         if not pd.view_events:
             return CooccurrenceModel({}, item_map, pd.items)
-        u = torch.tensor([user_map[v.user] for v in pd.view_events],
-                         dtype=torch.int64)
-        i = torch.tensor([item_map[v.item] for v in pd.view_events],
-                         dtype=torch.int64)
-        # user-distinct (view twice ≠ two pairs)
-        key = u * n_items + i
-        key = torch.unique(key)
-        u, i = key // n_items, key % n_items
         device = (torch.device("cuda") if torch.cuda.is_available()
                   else torch.device("cpu"))
-        A = torch.sparse_coo_tensor(
-            torch.stack([u, i]).to(device),
-            torch.ones(u.numel(), device=device),
-            (n_users, n_items)).coalesce()
-        with warnings.catch_warnings():
-            # torch's own "sparse CSR is beta" notice, not actionable
-            warnings.simplefilter("ignore", UserWarning)
-            C = torch.sparse.mm(A.t(), A).coalesce()
-        ii = C.indices()[0].cpu().numpy()
-        jj = C.indices()[1].cpu().numpy()
-        vv = C.values().cpu().numpy()
-        off = ii != jj  # drop the diagonal (item with itself)
-        ii, jj, vv = ii[off], jj[off], vv[off].astype(np.int64)
-        # per-item top-N: lexsort by (item, -count), take first n_keep
-        order = np.lexsort((-vv, ii))
-        ii, jj, vv = ii[order], jj[order], vv[order]
-        starts = np.flatnonzero(np.r_[True, ii[1:] != ii[:-1]])
+        u = torch.tensor([user_map[v.user] for v in pd.view_events],
+                         dtype=torch.int64, device=device)
+        i = torch.tensor([item_map[v.item] for v in pd.view_events],
+                         dtype=torch.int64, device=device)
+        # user-distinct (view twice ≠ two pairs): the op dedups the pairs
+        ids, cnt = cooccurrence_topn(u, i, n_users, n_items, n_keep)
+        top_ids, top_cnt = ids.cpu().numpy(), cnt.cpu().numpy()
         top_n: Dict[int, List[Tuple[int, int]]] = {}
-        bounds = np.r_[starts, len(ii)]
-        for s, e in zip(bounds[:-1], bounds[1:]):
-            e2 = min(e, s + n_keep)
-            top_n[int(ii[s])] = list(zip(jj[s:e2].tolist(),
-                                         vv[s:e2].tolist()))
-        return CooccurrenceModel(top_n, item_map, pd.items)
+        for it in (top_ids[:, 0] >= 0).nonzero()[0].tolist():
+            k = int((top_ids[it] >= 0).sum())
+            top_n[it] = list(zip(top_ids[it, :k].tolist(),
+                                 top_cnt[it, :k].tolist()))
+        return CooccurrenceModel(top_n, item_map, pd.items,
+                                 top_ids=top_ids, top_cnt=top_cnt)
 
     def predict(self, model: CooccurrenceModel, query) -> PredictedResult:
         q = query if isinstance(query, Query) else Query.from_json(query)
