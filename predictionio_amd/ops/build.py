@@ -11,13 +11,17 @@ import os
 import subprocess
 import sys
 import sysconfig
+import tempfile
 
 OPS_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(OPS_DIR, "csrc")
 SO_PATH = os.path.join(OPS_DIR, "_pio_hip.so")
 SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
            "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
-           "cooc_topn.hip"]
+           "cooc_topn.hip", "topk_cand.hip"]
+# compiled on their own with packed fp32 VALU ops off (the vectorizer may
+# otherwise pair independent fp32 chains), then linked with the rest
+NO_PACKED_FP32 = ["topk_cand.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -63,16 +67,32 @@ def build(force: bool = False, verbose: bool = True) -> str:
     ]
     for inc in tp["includes"]:
         cmd.append(f"-I{inc}")
-    cmd += [os.path.join(CSRC, s) for s in SOURCES]
-    cmd += [
-        f"-L{tp['libdir']}", f"-Wl,-rpath,{tp['libdir']}",
-        "-ltorch", "-ltorch_cpu", "-ltorch_python", "-ltorch_hip",
-        "-lc10", "-lc10_hip", "-lamdhip64",
-        "-o", SO_PATH,
-    ]
-    if verbose:
-        print("[ops.build]", " ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
+    with tempfile.TemporaryDirectory() as tmp:
+        objs = []
+        for s in NO_PACKED_FP32:
+            obj = os.path.join(tmp, os.path.splitext(s)[0] + ".o")
+            oc = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17",
+                  "-fPIC", "-D__HIP_PLATFORM_AMD__=1",
+                  "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+                  "-c", os.path.join(CSRC, s), "-o", obj]
+            if verbose:
+                print("[ops.build]", " ".join(oc), file=sys.stderr)
+            subprocess.run(oc, check=True)
+            objs.append(obj)
+        # objects first: hipcc puts `-x hip` before the first .cpp and
+        # would read anything after it as HIP source
+        cmd += objs
+        cmd += [os.path.join(CSRC, s) for s in SOURCES
+                if s not in NO_PACKED_FP32]
+        cmd += [
+            f"-L{tp['libdir']}", f"-Wl,-rpath,{tp['libdir']}",
+            "-ltorch", "-ltorch_cpu", "-ltorch_python", "-ltorch_hip",
+            "-lc10", "-lc10_hip", "-lamdhip64",
+            "-o", SO_PATH,
+        ]
+        if verbose:
+            print("[ops.build]", " ".join(cmd), file=sys.stderr)
+        subprocess.run(cmd, check=True)
     return SO_PATH
 
 

@@ -59,6 +59,13 @@ extern "C" void launch_cooc_topn(
 
 extern "C" int cooc_dense_lds_max();
 
+extern "C" void launch_topk_cand(
+    const float* Xq, const float* Y, const int* cand, const long long* segs,
+    int n_segs, const uint8_t* item_mask, const long long* ban_indptr,
+    const int* ban_indices, const int* item_cats, const int* query_cats,
+    int cw, int f, int K, int threads, float* out_val, int* out_idx,
+    float* scores, int grid, hipStream_t stream);
+
 namespace {
 
 void check_cuda_f32(const torch::Tensor& t, const char* name) {
@@ -551,6 +558,86 @@ void cooc_topn(torch::Tensor u_indptr, torch::Tensor u_items,
   C10_HIP_CHECK(hipGetLastError());
 }
 
+// Candidate-list top-K over a list of segments (see topk_cand.hip): each
+// row (query, lo, hi) of `segs` ranks cand_indices[lo..hi) for its query.
+// K in [1, 64] returns the segments' K best as (vals [n_segs, K] fp32,
+// idx [n_segs, K] i32), score descending then id ascending, empty slots
+// -inf / -1; threads (64 or 256) picks the instantiation. K = 0 is scores
+// mode: `scores` [nnz] receives every listed candidate's fp32 score, -inf
+// where it is filtered, and the returned tensors are empty. Xq and Y are
+// read where they lie, any rank 1 <= f <= 128. The candidate ids and the
+// segments are trusted: ops/topk.py range-checks the ids and builds the
+// segments from the checked CSR.
+std::tuple<torch::Tensor, torch::Tensor> topk_cand(
+    torch::Tensor Xq, torch::Tensor Y, torch::Tensor cand_indices,
+    torch::Tensor segs, int64_t K, int64_t threads,
+    c10::optional<torch::Tensor> item_mask,
+    c10::optional<torch::Tensor> ban_indptr,
+    c10::optional<torch::Tensor> ban_indices,
+    c10::optional<torch::Tensor> item_cats,
+    c10::optional<torch::Tensor> query_cats,
+    c10::optional<torch::Tensor> scores) {
+  check_cuda_f32(Xq, "Xq");
+  check_cuda_f32(Y, "Y");
+  TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2, "Xq and Y must be 2-D");
+  const int64_t B = Xq.size(0);
+  const int64_t N = Y.size(0);
+  const int64_t f = Y.size(1);
+  TORCH_CHECK(Xq.size(1) == f, "Xq/Y rank mismatch");
+  TORCH_CHECK(f >= 1 && f <= 128, "rank must be in [1, 128], got ", f);
+  TORCH_CHECK(N < (1LL << 31), "item count must be below 2^31");
+  TORCH_CHECK(cand_indices.is_cuda() && cand_indices.is_contiguous() &&
+                  cand_indices.scalar_type() == torch::kInt32 &&
+                  cand_indices.dim() == 1,
+              "cand_indices must be a contiguous 1-D i32 GPU tensor");
+  TORCH_CHECK(segs.is_cuda() && segs.is_contiguous() &&
+                  segs.scalar_type() == torch::kInt64 && segs.dim() == 2 &&
+                  segs.size(1) == 3,
+              "segs must be a contiguous [n, 3] i64 GPU tensor");
+  TORCH_CHECK(threads == 64 || threads == 256, "threads must be 64 or 256");
+  TORCH_CHECK(K >= 0 && K <= 64, "K must be in [0, 64]");
+  TORCH_CHECK((K == 0) == scores.has_value(),
+              "scores goes with K = 0 and only with it");
+  const auto dev = Xq.device();
+  TORCH_CHECK(Y.device() == dev && cand_indices.device() == dev &&
+                  segs.device() == dev,
+              "all tensors must be on one device");
+  const TopkArgs a = check_topk_args(item_mask, ban_indptr, ban_indices,
+                                     c10::nullopt, item_cats, query_cats, B,
+                                     N);
+  const int64_t n_segs = segs.size(0);
+  TORCH_CHECK(n_segs < (1LL << 31), "too many segments for one launch");
+  float* scores_ptr = nullptr;
+  if (scores.has_value()) {
+    check_cuda_f32(*scores, "scores");
+    TORCH_CHECK(scores->dim() == 1 &&
+                    scores->size(0) == cand_indices.size(0) &&
+                    scores->device() == dev,
+                "scores must be [nnz] on Xq's device");
+    scores_ptr = scores->data_ptr<float>();
+  }
+  auto out_val = torch::empty({K == 0 ? 0 : n_segs, K}, Xq.options());
+  auto out_idx = torch::empty({K == 0 ? 0 : n_segs, K},
+                              Xq.options().dtype(torch::kInt32));
+  if (n_segs == 0) return {out_val, out_idx};
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const int n_cu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  const int thr = K == 0 ? 256 : (int)threads;
+  // 32 waves per CU either way: 32 one-wave or 8 four-wave workgroups
+  const int64_t grid =
+      std::min<int64_t>(n_segs, (int64_t)n_cu * (thr == 64 ? 32 : 8));
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_topk_cand(
+      Xq.data_ptr<float>(), Y.data_ptr<float>(), cand_indices.data_ptr<int>(),
+      reinterpret_cast<const long long*>(segs.data_ptr<int64_t>()),
+      (int)n_segs, a.mask, a.ban_indptr, a.ban_indices, a.item_cats,
+      a.query_cats, a.cw, (int)f, (int)K, thr, out_val.data_ptr<float>(),
+      out_idx.data_ptr<int>(), scores_ptr, (int)grid, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {out_val, out_idx};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -592,6 +679,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("u_indptr"), py::arg("u_items"), py::arg("i_indptr"),
         py::arg("i_users"), py::arg("rows"), py::arg("n"), py::arg("tier"),
         py::arg("pool"), py::arg("top_ids"), py::arg("top_cnt"));
+  m.def("topk_cand", &topk_cand,
+        "Candidate-list top-K (or scores) over a list of segments",
+        py::arg("Xq"), py::arg("Y"), py::arg("cand_indices"),
+        py::arg("segs"), py::arg("K"), py::arg("threads"),
+        py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
+        py::arg("ban_indices") = py::none(),
+        py::arg("item_cats") = py::none(), py::arg("query_cats") = py::none(),
+        py::arg("scores") = py::none());
   m.def("cooc_dense_lds_max", &cooc_dense_lds_max,
         "Largest item count of the LDS dense tier");
 }

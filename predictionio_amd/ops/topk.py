@@ -58,7 +58,9 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                mode: Optional[str] = None,
                item_cats: Optional[torch.Tensor] = None,
                query_cats: Optional[torch.Tensor] = None,
-               list_k: Optional[int] = None
+               list_k: Optional[int] = None,
+               cand_indptr: Optional[torch.Tensor] = None,
+               cand_indices: Optional[torch.Tensor] = None
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K of (Xq @ Y.T) per query row, with optional global item mask
     (uint8, 1=banned) and per-query banned lists (CSR int32, sorted).
@@ -88,11 +90,25 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     syncs with the host) and PIO_TOPK_UNION=0. mode="union" forces the
     union path at any K >= 1 (ValueError when the shape admits no plan);
     list_k with n_slices pins its plan. K > 64 without the union path,
-    and any K > 1024, use the materialized fallback, which is exact."""
+    and any K > 1024, use the materialized fallback, which is exact.
+
+    cand_indptr [B+1] int64 / cand_indices int32 (a CSR, given together,
+    ids strictly ascending within a query) restrict query b to its own
+    candidate list: only the listed rows of Y are read, the three filters
+    apply as above, and the result is exact fp32 in the order score
+    descending, id ascending on equal scores (_topk_score_cands on GPU
+    in every mode, topk_score_cands_ref on CPU)."""
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
     _check_cats(item_cats, query_cats, B, N)
+    if (cand_indptr is None) != (cand_indices is None):
+        raise ValueError(
+            "cand_indptr and cand_indices must be given together")
+    if cand_indptr is not None:
+        fn = _topk_score_cands if Xq.is_cuda else topk_score_cands_ref
+        return fn(Xq, Y, K, cand_indptr, cand_indices, item_mask,
+                  ban_indptr, ban_indices, item_cats, query_cats)
     if Xq.is_cuda:
         if mode is None:
             mode = os.environ.get("PIO_TOPK_MODE", "mfma")
@@ -492,10 +508,224 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     return mv, midx
 
 
+_cand_stats: Dict[str, int] = {"calls": 0, "queries": 0, "segments": 0}
+
+
+def cand_stats() -> Dict[str, int]:
+    """Cumulative counters of the candidate-list path since import:
+    calls, queries served, and segments launched."""
+    return dict(_cand_stats)
+
+
+def _check_cands(cand_indptr: torch.Tensor, cand_indices: torch.Tensor,
+                 B: int, N: int, seg_len: int, wave_max: int):
+    """The candidate-CSR contract, checked on the tensors' device with one
+    transfer to the host: cand_indptr [B+1] int64 runs from 0 to nnz
+    without decreasing; cand_indices int32 holds ids in [0, N), strictly
+    ascending inside every query. An out-of-range id would be an
+    out-of-bounds gather and a repeated one breaks the selection's
+    distinct-key premise, so each raises ValueError. Returns (lens [B],
+    segments, segments longer than wave_max, most segments of a query)
+    for lists cut every seg_len candidates."""
+    ip, ci = cand_indptr, cand_indices
+    if ip.dtype != torch.int64 or ip.dim() != 1 or ip.numel() != B + 1:
+        raise ValueError("cand_indptr must be a 1-D int64 tensor of B + 1")
+    if ci.dtype != torch.int32 or ci.dim() != 1:
+        raise ValueError("cand_indices must be a 1-D int32 tensor")
+    if ip.device != ci.device:
+        raise ValueError("cand_indptr and cand_indices must share a device")
+    nnz = ci.numel()
+    lens = ip[1:] - ip[:-1]
+    is_start = torch.zeros(nnz + 1, dtype=torch.bool, device=ci.device)
+    is_start[ip.clamp(0, nnz)] = True
+    full, rem = lens.clamp_min(0) // seg_len, lens.clamp_min(0) % seg_len
+    nseg_q = full + (rem > 0)
+    zero = torch.zeros((), dtype=torch.int64, device=ci.device)
+    bad_ptr, bad_len, bad_id, bad_order, n_seg, n_long, max_seg = \
+        torch.stack([
+            (ip[0] != 0) | (ip[-1] != nnz),
+            (lens < 0).any(),
+            ((ci < 0) | (ci >= N)).any(),
+            ((ci[1:] <= ci[:-1]) & ~is_start[1:nnz]).any(),
+            nseg_q.sum(),
+            (full * int(seg_len > wave_max) + (rem > wave_max)).sum(),
+            nseg_q.max() if B else zero,
+        ]).tolist()
+    if bad_ptr:
+        raise ValueError("cand_indptr must run from 0 to len(cand_indices)")
+    if bad_len:
+        raise ValueError("cand_indptr must not decrease")
+    if bad_id:
+        raise ValueError(f"cand_indices holds an id outside [0, {N})")
+    if bad_order:
+        raise ValueError("cand_indices must be strictly ascending inside "
+                         "every query (sorted, no duplicates)")
+    return lens, n_seg, n_long, max_seg
+
+
+def _cand_order_key(score: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """int64 keys whose descending order is score descending, then id
+    ascending: the kernel's (ord(score) << 32) | (0xFFFFFFFF - id) with
+    ord shifted by 2^31 into the signed range. Empty slots (id -1) are
+    keyed as id 0; their -inf score puts them last anyway."""
+    u = score.contiguous().view(torch.int32).long()
+    o = torch.where(u >= 0, u, -u - 1 - 2 ** 31)
+    return (o << 32) | (0xFFFFFFFF - ids.long().clamp_min(0))
+
+
+def _cand_select(qid: torch.Tensor, score: torch.Tensor, ids: torch.Tensor,
+                 B: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The K best (score, id) pairs of every query from flat pairs tagged
+    with their query: two sorts (key descending, then query, stable) and
+    a scatter by rank. O(pairs) memory; -inf scores become -inf / -1."""
+    dev = score.device
+    n = score.numel()
+    o1 = torch.argsort(_cand_order_key(score, ids), descending=True)
+    perm = o1[torch.argsort(qid[o1], stable=True)]
+    qs = qid[perm]
+    counts = torch.bincount(qid, minlength=B)
+    rank = torch.arange(n, device=dev) - (torch.cumsum(counts, 0)
+                                          - counts)[qs]
+    slot = torch.where(rank < K, qs * K + rank, B * K)  # B * K: dropped
+    vals = torch.full((B * K + 1,), float("-inf"), device=dev)
+    idx = torch.full((B * K + 1,), -1, dtype=torch.int64, device=dev)
+    vals[slot] = score[perm]
+    idx[slot] = ids[perm].long()
+    vals, idx = vals[:-1].view(B, K), idx[:-1].view(B, K)
+    idx[vals == float("-inf")] = -1
+    return vals, idx
+
+
+def _topk_score_cands(Xq: torch.Tensor, Y: torch.Tensor, K: int,
+                      cand_indptr: torch.Tensor, cand_indices: torch.Tensor,
+                      item_mask=None, ban_indptr=None, ban_indices=None,
+                      item_cats=None, query_cats=None,
+                      seg_len: int = 8192, wave_max: int = 256
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Candidate-list top-K on the GPU (csrc/topk_cand.hip): every query
+    ranks its own CSR list, reading only the listed rows of Y. Exact
+    fp32; order score descending, id ascending. Xq and Y are read where
+    they lie (contiguous fp32, any rank 1..128) — no padding, no copy.
+
+    Lists longer than seg_len are cut into segments of at most seg_len
+    candidates so that one huge list (or B = 1) still fills the chip;
+    segments of at most wave_max candidates run in the one-wave
+    instantiation, longer ones in the 256-thread one. A query with
+    several segments has its segments * K pairs merged by _cand_select,
+    which equals the unsegmented result because a candidate's score does
+    not depend on its segment. K > 64 runs the kernel's scores mode
+    (every candidate's score into an [nnz] buffer) and the same
+    device-side sort: O(nnz) memory. Syncs with the host once (the
+    checks), so not under stream capture."""
+    from predictionio_amd.ops import hip_ext
+    B, f = Xq.shape
+    N = Y.shape[0]
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    if seg_len < 1 or wave_max < 0:
+        raise ValueError("seg_len must be >= 1 and wave_max >= 0")
+    for name, t in (("Xq", Xq), ("Y", Y)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous fp32: the candidate"
+                             " kernel reads it where it lies")
+    if not 1 <= f <= 128 or Y.shape[1] != f:
+        raise ValueError("rank must be in [1, 128] and equal for Xq and Y")
+    lens, n_seg, n_long, max_seg = _check_cands(
+        cand_indptr, cand_indices, B, N, seg_len, wave_max)
+    _cand_stats["calls"] += 1
+    _cand_stats["queries"] += B
+    _cand_stats["segments"] += n_seg
+    dev = Xq.device
+    if n_seg == 0:
+        return (torch.full((B, K), float("-inf"), device=dev),
+                torch.full((B, K), -1, dtype=torch.int64, device=dev))
+    # the work list: (query, lo, hi), heaviest first
+    full, rem = lens // seg_len, lens % seg_len
+    nseg_q = full + (rem > 0)
+    seg_q = torch.repeat_interleave(torch.arange(B, device=dev), nseg_q,
+                                    output_size=n_seg)
+    k = (torch.arange(n_seg, device=dev)
+         - (torch.cumsum(nseg_q, 0) - nseg_q)[seg_q])
+    lo = cand_indptr[seg_q] + k * seg_len
+    hi = torch.minimum(lo + seg_len, cand_indptr[seg_q + 1])
+    order = torch.argsort(hi - lo, descending=True, stable=True)
+    segs = torch.stack([seg_q, lo, hi], 1)[order].contiguous()
+    kw = dict(
+        item_mask=item_mask.contiguous() if item_mask is not None else None,
+        ban_indptr=ban_indptr.contiguous() if ban_indptr is not None
+        else None,
+        ban_indices=ban_indices.contiguous() if ban_indices is not None
+        else None,
+        item_cats=item_cats, query_cats=query_cats)
+    ext = hip_ext()
+    ci = cand_indices.contiguous()
+    if K > 64:
+        scores = torch.empty(ci.numel(), dtype=torch.float32, device=dev)
+        ext.topk_cand(Xq, Y, ci, segs, 0, 256, scores=scores, **kw)
+        qid = torch.repeat_interleave(torch.arange(B, device=dev), lens,
+                                      output_size=ci.numel())
+        return _cand_select(qid, scores, ci, B, K)
+    parts = []
+    if n_long:
+        parts.append(ext.topk_cand(Xq, Y, ci, segs[:n_long], K, 256, **kw))
+    if n_seg > n_long:
+        parts.append(ext.topk_cand(Xq, Y, ci, segs[n_long:], K, 64, **kw))
+    sv = torch.cat([p[0] for p in parts])
+    si = torch.cat([p[1] for p in parts])
+    sq = segs[:, 0]
+    if max_seg > 1:
+        return _cand_select(sq.repeat_interleave(K), sv.flatten(),
+                            si.flatten(), B, K)
+    vals = torch.full((B, K), float("-inf"), device=dev)
+    idx = torch.full((B, K), -1, dtype=torch.int64, device=dev)
+    vals[sq] = sv
+    idx[sq] = si.long()
+    return vals, idx
+
+
+def topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
+                         item_mask=None, ban_indptr=None, ban_indices=None,
+                         item_cats=None, query_cats=None
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Pure-torch candidate-list top-K (CPU path + GPU numerics
+    baseline): gather the candidate rows, score, filter, and order by
+    score descending then id ascending. O(nnz * f) memory."""
+    B, N = Xq.shape[0], Y.shape[0]
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    _check_cats(item_cats, query_cats, B, N)
+    lens, _, _, _ = _check_cands(cand_indptr, cand_indices, B, N,
+                                 1 << 62, 1 << 62)
+    dev = Xq.device
+    qid = torch.repeat_interleave(torch.arange(B, device=dev), lens)
+    j = cand_indices.long()
+    score = (Xq.float()[qid] * Y.float()[j]).sum(dim=1)
+    ok = torch.ones_like(j, dtype=torch.bool)
+    if item_mask is not None:
+        ok &= ~item_mask.bool()[j]
+    if item_cats is not None:
+        ok &= ((item_cats[j] & query_cats[qid]) != 0).any(dim=1)
+    if ban_indptr is not None:
+        bq = torch.repeat_interleave(torch.arange(B, device=dev),
+                                     ban_indptr[1:] - ban_indptr[:-1])
+        ok &= ~torch.isin(qid * N + j, bq * N + ban_indices.long())
+    score = score.masked_fill(~ok, float("-inf"))
+    return _cand_select(qid, score, cand_indices, B, K)
+
+
 def topk_score_ref(Xq, Y, K, item_mask=None, ban_indptr=None,
-                   ban_indices=None, item_cats=None, query_cats=None
+                   ban_indices=None, item_cats=None, query_cats=None,
+                   cand_indptr=None, cand_indices=None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch reference (CPU path + GPU numerics baseline)."""
+    if (cand_indptr is None) != (cand_indices is None):
+        raise ValueError(
+            "cand_indptr and cand_indices must be given together")
+    if cand_indptr is not None:
+        return topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
+                                    item_mask, ban_indptr, ban_indices,
+                                    item_cats, query_cats)
     _check_cats(item_cats, query_cats, Xq.shape[0], Y.shape[0])
     scores = Xq.float() @ Y.float().t()  # B x N
     if item_cats is not None:

@@ -33,7 +33,9 @@ def sharded_topk_score(Xq: torch.Tensor, Y_local: torch.Tensor, K: int,
     lists are in LOCAL shard coordinates. The optional category filter
     follows the same split: `item_cats` is row-sharded like `Y_local`,
     `query_cats` is replicated like `Xq`. Returns (values, global
-    indices) identical on every rank.
+    indices) identical on every rank. It does not take candidate lists
+    (`topk_score(..., cand_indptr=, cand_indices=)`): a list would have
+    to be split by shard first.
     """
     v, idx = topk_ops.topk_score(Xq, Y_local, K, item_mask=item_mask,
                                  ban_indptr=ban_indptr,

@@ -350,16 +350,17 @@ class ECommAlgorithm(Algorithm):
             pass
         return set()
 
-    def _mask(self, model: ECommModel, q: Query, black: Set[str]
-              ) -> torch.Tensor:
+    def _mask(self, model: ECommModel, q: Query, black: Set[str],
+              white: bool = True) -> torch.Tensor:
         """Device-resident filters: category membership from train-time
         masks, white/black lists as small index_put ops — query cost is
-        flat in catalog size."""
+        flat in catalog size. white=False leaves the whiteList out (the
+        caller passes it to the kernel as a candidate list instead)."""
         from predictionio_amd.templates.common import ids_tensor
         dev = model.item_factors.device
         n = len(model.item_map)
         mask = torch.zeros(n, dtype=torch.uint8, device=dev)
-        if q.white_list is not None:
+        if white and q.white_list is not None:
             mask[:] = 1
             mask[ids_tensor(q.white_list, model.item_map, dev)] = 0
         if q.categories is not None:
@@ -390,19 +391,35 @@ class ECommAlgorithm(Algorithm):
 
     # ------------------------------------------------------------ predict
 
-    def _topk(self, model, Xq, mask, num) -> List[ItemScore]:
-        v, idx = topk_ops.topk_score(Xq, model.item_factors, num,
-                                     item_mask=mask)
+    @staticmethod
+    def _cands(model, q: Query) -> Optional[List[int]]:
+        """The whiteList as a sorted candidate list of item rows, or None
+        when the query has none."""
+        if q.white_list is None:
+            return None
+        return sorted({model.item_map[x] for x in q.white_list
+                       if x in model.item_map})
+
+    def _topk(self, model, Xq, mask, num, cands=None,
+              Y=None) -> List[ItemScore]:
+        """One query's top-K over Y (item_factors by default). With
+        `cands` (a sorted list of item rows) only those rows are read."""
+        from predictionio_amd.templates.common import ban_csr
+        Y = model.item_factors if Y is None else Y
+        kw = {}
+        if cands is not None:
+            kw["cand_indptr"], kw["cand_indices"] = ban_csr([cands],
+                                                            Y.device)
+        v, idx = topk_ops.topk_score(Xq.contiguous(), Y, num,
+                                     item_mask=mask, **kw)
         v, idx = v[0].cpu(), idx[0].cpu()
         return [ItemScore(model.item_inv[int(i)], float(s))
                 for s, i in zip(v, idx) if i >= 0]
 
-    def _topk_cos(self, model, Xq, mask, num) -> List[ItemScore]:
-        v, idx = topk_ops.topk_score(Xq, model.item_factors_norm, num,
-                                     item_mask=mask)
-        v, idx = v[0].cpu(), idx[0].cpu()
-        return [ItemScore(model.item_inv[int(i)], float(s))
-                for s, i in zip(v, idx) if i >= 0]
+    def _topk_cos(self, model, Xq, mask, num, cands=None
+                  ) -> List[ItemScore]:
+        return self._topk(model, Xq, mask, num, cands,
+                          model.item_factors_norm)
 
     def _recent_items(self, q: Query) -> List[str]:
         """Latest N similarEvents of the user (getRecentItems :430-467)."""
@@ -420,11 +437,13 @@ class ECommAlgorithm(Algorithm):
     def predict(self, model: ECommModel, query) -> PredictedResult:
         q = query if isinstance(query, Query) else Query.from_json(query)
         black = self._gen_black_list(q)
-        mask = self._mask(model, q, black)
+        # a whiteList is the kernel's candidate list, not an N-byte mask
+        cands = self._cands(model, q)
+        mask = self._mask(model, q, black, white=False)
         uidx = model.user_map.get(q.user)
         if uidx is not None and uidx < model.user_features.shape[0]:
             scores = self._topk(model, model.user_features[uidx:uidx + 1],
-                                mask, q.num)
+                                mask, q.num, cands)
         else:
             recent = [model.item_map[i] for i in self._recent_items(q)
                       if i in model.item_map]
@@ -433,33 +452,30 @@ class ECommAlgorithm(Algorithm):
                 Xq = model.item_factors_norm[
                     torch.tensor(recent, device=dev)].sum(dim=0,
                                                           keepdim=True)
-                scores = self._topk_cos(model, Xq, mask, q.num)
+                scores = self._topk_cos(model, Xq, mask, q.num, cands)
             else:
-                scores = self._predict_default(model, mask, q)
+                scores = self._predict_default(
+                    model, self._mask(model, q, black), q)
         return PredictedResult(self._apply_weights(model, scores)[:q.num])
 
     def batch_predict(self, model: ECommModel, queries):
         """Device-batched predict: at most two fused top-K launches for
         the whole batch (known users over item_factors, cold users with
-        recent views over item_factors_norm). Per query, `categories`
-        becomes a row of category bit words and blackList + seen items a
-        sorted ban list in one CSR; the unavailableItems constraint is
-        fetched once per batch and becomes the shared item_mask. Live
-        per-user lookups stay per query. Queries with a whiteList (rare,
-        and a batch-wide mask does not fit them) and models without
-        category bits go through predict() one by one."""
+        recent views over item_factors_norm), plus one candidate-list
+        launch per group for its whiteList queries. Per query,
+        `categories` becomes a row of category bit words, blackList +
+        seen items a sorted ban list in one CSR and a whiteList a row of
+        the candidate CSR; the unavailableItems constraint is fetched
+        once per batch and becomes the shared item_mask. Live per-user
+        lookups stay per query. Models without category bits go through
+        predict() one by one."""
         qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
               for i, q in queries]
         bits = model.cat_bits()
         out: Dict[int, PredictedResult] = {}
         if bits is None:
             return [(i, self.predict(model, q)) for i, q in qs]
-        batch = []
-        for i, q in qs:
-            if q.white_list is not None:
-                out[i] = self.predict(model, q)
-            else:
-                batch.append((i, q))
+        batch = qs
         if batch:
             dev = model.item_factors.device
             n = len(model.item_map)
@@ -488,29 +504,45 @@ class ECommAlgorithm(Algorithm):
                         model, self._predict_default(
                             model, self._mask(model, q, black | unavailable),
                             q))[:q.num])
-            if known:
-                Xq = model.user_features[
-                    torch.tensor([g[3] for g in known], device=dev)]
-                self._batch_topk(model, bits, known, Xq,
-                                 model.item_factors, item_mask, out)
-            if cold:
-                rows = torch.tensor([r for g in cold for r in g[3]],
-                                    device=dev)
-                seg = torch.tensor(
-                    [k for k, g in enumerate(cold) for _ in g[3]],
-                    device=dev)
-                Yn = model.item_factors_norm
-                Xq = torch.zeros((len(cold), Yn.shape[1]), dtype=Yn.dtype,
-                                 device=dev).index_add_(0, seg, Yn[rows])
-                self._batch_topk(model, bits, cold, Xq, Yn, item_mask, out)
+            # each group: its plain queries, then its whiteList queries
+            for white in (False, True):
+                sub = [g for g in known
+                       if (g[1].white_list is not None) == white]
+                if sub:
+                    Xq = model.user_features[
+                        torch.tensor([g[3] for g in sub], device=dev)]
+                    self._batch_topk(model, bits, sub, Xq,
+                                     model.item_factors, item_mask, out,
+                                     white)
+                sub = [g for g in cold
+                       if (g[1].white_list is not None) == white]
+                if sub:
+                    rows = torch.tensor([r for g in sub for r in g[3]],
+                                        device=dev)
+                    seg = torch.tensor(
+                        [k for k, g in enumerate(sub) for _ in g[3]],
+                        device=dev)
+                    Yn = model.item_factors_norm
+                    Xq = torch.zeros((len(sub), Yn.shape[1]),
+                                     dtype=Yn.dtype, device=dev
+                                     ).index_add_(0, seg, Yn[rows])
+                    self._batch_topk(model, bits, sub, Xq, Yn, item_mask,
+                                     out, white)
         return [(i, out[i]) for i, _ in qs]
 
-    def _batch_topk(self, model, bits, group, Xq, Y, item_mask, out):
+    def _batch_topk(self, model, bits, group, Xq, Y, item_mask, out,
+                    white=False):
         """One fused launch for `group` [(i, q, ban list, _)]; K is the
-        group's largest num and every result is cut to its own."""
+        group's largest num and every result is cut to its own. white:
+        every query of the group has a whiteList, which becomes its row
+        of the candidate CSR."""
         import numpy as np
         from predictionio_amd.templates.common import ban_csr
         dev = Y.device
+        kw = {}
+        if white:
+            kw["cand_indptr"], kw["cand_indices"] = ban_csr(
+                [self._cands(model, g[1]) for g in group], dev)
         ban_indptr, ban_indices = ban_csr([g[2] for g in group], dev)
         query_cats = torch.from_numpy(np.stack(
             [bits.query_words(g[1].categories) for g in group])).to(dev)
@@ -518,7 +550,7 @@ class ECommAlgorithm(Algorithm):
         v, ix = topk_ops.topk_score(
             Xq, Y, num, item_mask=item_mask, ban_indptr=ban_indptr,
             ban_indices=ban_indices, item_cats=bits.item_words,
-            query_cats=query_cats)
+            query_cats=query_cats, **kw)
         v_np = v.cpu().numpy()
         ix_np = ix.cpu().numpy()
         names = model.item_inv_np()[np.clip(ix_np, 0, None)]

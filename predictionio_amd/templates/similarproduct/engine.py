@@ -221,16 +221,15 @@ class ALSAlgorithm(Algorithm):
 
     def _masks(self, model: SimilarModel, q: Query,
                dev) -> Optional[torch.Tensor]:
-        """uint8 banned mask from white/black/category filters
+        """uint8 banned mask from black/category filters
         (ALSAlgorithm.scala:245-271 isCandidateItem). Device-resident:
-        category membership comes from train-time masks, white/black
-        lists are small index_put ops — nothing scans the catalog."""
+        category membership comes from train-time masks, the blackList
+        is a small index_put op — nothing scans the catalog. A whiteList
+        is not part of the mask: it goes to the kernel as the query's
+        candidate list (_cands)."""
         from predictionio_amd.templates.common import ids_tensor
         n = len(model.item_map)
         mask = None
-        if q.white_list is not None:
-            mask = torch.ones(n, dtype=torch.uint8, device=dev)
-            mask[ids_tensor(q.white_list, model.item_map, dev)] = 0
         if q.categories is not None:
             cm = model.cat_masks().banned_outside(q.categories).to(dev)
             mask = cm if mask is None else (mask | cm)
@@ -244,7 +243,19 @@ class ALSAlgorithm(Algorithm):
         mask[ids_tensor(q.items, model.item_map, dev)] = 1
         return mask
 
+    # batch_predict keeps whiteList queries in the batch (one candidate-
+    # list launch); False sends each through predict(), which passes its
+    # own one-row candidate list
+    batch_white_lists = True
+
+    @staticmethod
+    def _cands(model, q: Query) -> List[int]:
+        """The whiteList as a sorted candidate list of item rows."""
+        return sorted({model.item_map[x] for x in q.white_list
+                       if x in model.item_map})
+
     def predict(self, model: SimilarModel, query) -> PredictedResult:
+        from predictionio_amd.templates.common import ban_csr
         q = query if isinstance(query, Query) else Query.from_json(query)
         rows = [model.item_map[i] for i in q.items
                 if i in model.item_map]
@@ -255,8 +266,12 @@ class ALSAlgorithm(Algorithm):
         Xq = model.item_factors_norm[torch.tensor(rows, device=dev)] \
             .sum(dim=0, keepdim=True)
         mask = self._masks(model, q, dev)
+        kw = {}
+        if q.white_list is not None:
+            kw["cand_indptr"], kw["cand_indices"] = ban_csr(
+                [self._cands(model, q)], dev)
         v, idx = topk_ops.topk_score(Xq, model.item_factors_norm, q.num,
-                                     item_mask=mask)
+                                     item_mask=mask, **kw)
         v, idx = v[0].cpu(), idx[0].cpu()
         return PredictedResult([
             ItemScore(model.item_inv[int(i)], float(s))
@@ -264,12 +279,13 @@ class ALSAlgorithm(Algorithm):
 
     def batch_predict(self, model: SimilarModel, queries):
         """Device-batched predict: ONE fused top-K launch over
-        item_factors_norm for the whole batch. Per query, `categories`
-        becomes a row of category bit words, and blackList + the query's
-        own items a sorted ban list in one CSR. Queries with no known
-        item give an empty result; queries with a whiteList (rare, and a
-        batch-wide mask does not fit them) and models without category
-        bits go through predict() one by one."""
+        item_factors_norm for the batch's plain queries and one
+        candidate-list launch for its whiteList queries. Per query,
+        `categories` becomes a row of category bit words, blackList +
+        the query's own items a sorted ban list in one CSR, and a
+        whiteList a row of the candidate CSR. Queries with no known item
+        give an empty result; models without category bits go through
+        predict() one by one."""
         import numpy as np
         from predictionio_amd.templates.common import ban_csr
         qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
@@ -282,18 +298,20 @@ class ALSAlgorithm(Algorithm):
             return [(i, ALSAlgorithm.predict(self, model, q))
                     for i, q in qs]
         out: Dict[int, PredictedResult] = {}
-        group = []  # (i, q, query item rows)
+        groups = ([], [])  # (i, q, query item rows): plain, whiteList
         for i, q in qs:
-            if q.white_list is not None:
+            if q.white_list is not None and not self.batch_white_lists:
                 out[i] = ALSAlgorithm.predict(self, model, q)
                 continue
             rows = [model.item_map[x] for x in q.items
                     if x in model.item_map]
             if rows:
-                group.append((i, q, rows))
+                groups[q.white_list is not None].append((i, q, rows))
             else:
                 out[i] = PredictedResult([])
-        if group:
+        for white, group in enumerate(groups):
+            if not group:
+                continue
             Yn = model.item_factors_norm
             dev = Yn.device
             # sum of cosines = (sum of normalized query vectors) . Yn
@@ -312,9 +330,13 @@ class ALSAlgorithm(Algorithm):
             query_cats = torch.from_numpy(np.stack(
                 [bits.query_words(g[1].categories) for g in group])).to(dev)
             num = max(g[1].num for g in group)
+            kw = {}
+            if white:
+                kw["cand_indptr"], kw["cand_indices"] = ban_csr(
+                    [self._cands(model, g[1]) for g in group], dev)
             v, ix = topk_ops.topk_score(
                 Xq, Yn, num, ban_indptr=ban_indptr, ban_indices=ban_indices,
-                item_cats=bits.item_words, query_cats=query_cats)
+                item_cats=bits.item_words, query_cats=query_cats, **kw)
             v_np = v.cpu().numpy()
             ix_np = ix.cpu().numpy()
             names = model.item_inv_np()[np.clip(ix_np, 0, None)]
@@ -466,7 +488,11 @@ class FollowDataSource(BaseDataSource):
 class RecommendedUserAlgorithm(ALSAlgorithm):
     """Trains implicit ALS on follow events; the 'item' side is the
     followed users, so predict returns similar USERS
-    (recommended-user ALSAlgorithm.scala)."""
+    (recommended-user ALSAlgorithm.scala). Its whiteList queries keep
+    the per-query route of batch_predict (each a one-row candidate-list
+    call)."""
+
+    batch_white_lists = False
 
     def predict(self, model: SimilarModel, query) -> PredictedResult:
         q = query if isinstance(query, UserQuery) \
