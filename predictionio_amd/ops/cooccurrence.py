@@ -14,6 +14,33 @@ memory is O(nnz + N n + a fixed counter pool) and no pair data goes
 through the host. On CPU tensors cooccurrence_topn_ref (torch.sparse.mm
 plus a vectorised top-n) is the implementation; it materialises the
 item x item product and is what the GPU tests compare against.
+
+Cross-occurrence and LLR. cross_occurrence_topn takes two deduplicated
+pair sets over the same U = n_users users, A over Na row items and B
+over Nb column items ("viewed this, bought ..."). For a row item i and
+a column item j
+
+    k11 = |usersA(i) ∩ usersB(j)|    Ai = |usersA(i)|   Bj = |usersB(j)|
+    k12 = Ai - k11    k21 = Bj - k11    k22 = U - Ai - Bj + k11
+    xlx(x) = x ln x,  xlx(0) = 0
+
+    llr = max(0, 2 (xlx(U) - xlx(Ai) - xlx(U - Ai) - xlx(Bj) - xlx(U - Bj)
+                    + xlx(k11) + xlx(k12) + xlx(k21) + xlx(k22)))
+
+which is Mahout's LogLikelihood.logLikelihoodRatio (row entropy + column
+entropy - matrix entropy, clamped at 0) with the terms separated into a
+per-row part R_i = xlx(U) - xlx(Ai) - xlx(U - Ai), a per-column part
+H_j = xlx(Bj) + xlx(U - Bj) and four per-pair terms. A pair that is
+merely popular scores near 0. Candidates of row i are the j with
+k11 > 0 and, with exclude_self (needs Na == Nb), j != i. score="count"
+ranks them by k11 as above; score="llr" by llr: row i holds the n
+candidates with the largest score, score descending and id ascending on
+equal fp32 scores, the descending order of
+(bits(float(llr)) << 32) | (0xFFFFFFFF - j) (llr >= 0, so the raw fp32
+bits are order-preserving; the key is never 0 and distinct per j).
+Unused slots are id -1, score 0. The sum is formed in fp64 and rounded
+to fp32 once: the terms reach U ln U (1.4e7 at a million users) and
+cancel down to order 1, fp32 would keep no digits.
 """
 
 from __future__ import annotations
@@ -79,12 +106,23 @@ def build_csrs(users, items, n_users: int, n_items: int):
 
 
 def cooccurrence_plan(u_indptr, i_indptr, i_users, n_items: int,
-                      hash_caps=HASH_CAPS):
+                      hash_caps=HASH_CAPS, *, exclude_self: bool = True,
+                      cross: bool = False):
     """Route the item rows to tiers. With d the user degrees, per item
 
         deg_i  = its user count
         work_i = sum of d_u over its users (pair visits incl. itself)
         ub_i   = min(N - 1, work_i - deg_i) >= its distinct neighbours
+
+    Cross form (cross=True): (i_indptr, i_users) is the item-major CSR
+    of the row side A, u_indptr the user-major row pointers of the
+    column side B (d = dB), n_items = Nb, and with s = 1 if exclude_self
+    else 0
+
+        ub_i   = min(Nb - s, work_i)
+
+    (work_i - s * deg_i would assume that every user of i in A also has
+    i in B, which only the self form guarantees.)
 
     Returns three int32 row lists — ub <= hash_caps[0], ub <=
     hash_caps[1], the rest — each sorted by work descending, so the
@@ -98,7 +136,9 @@ def cooccurrence_plan(u_indptr, i_indptr, i_users, n_items: int,
                      device=i_users.device)
     cs[1:] = d[i_users.long()].cumsum(0)
     work = cs[i_indptr[1:]] - cs[i_indptr[:-1]]
-    ub = torch.clamp(work - deg, max=int(n_items) - 1)
+    s = 1 if exclude_self else 0
+    ub = torch.clamp(work if cross else work - s * deg,
+                     max=int(n_items) - s)
     live = (deg > 0) & (ub > 0)
     order = torch.argsort(work, descending=True, stable=True)
     ub_o, live_o = ub[order], live[order]
@@ -108,45 +148,92 @@ def cooccurrence_plan(u_indptr, i_indptr, i_users, n_items: int,
     return tuple(order[m].to(torch.int32) for m in tiers)
 
 
-def cooccurrence_topn_ref(users, items, n_users: int, n_items: int, n: int):
-    """Plain torch reference: sparse A^T A, diagonal dropped, packed keys
-    sorted, scattered into [N, n]. Any n >= 1. Memory grows with the
-    number of distinct co-occurring pairs."""
+def _xlx(x):
+    x = x.to(torch.float64)
+    return torch.xlogy(x, x)
+
+
+def _check_score(score: str) -> bool:
+    if score not in ("count", "llr"):
+        raise ValueError(f'score must be "count" or "llr", got {score!r}')
+    return score == "llr"
+
+
+def cross_occurrence_topn_ref(users_a, items_a, n_items_a: int, users_b,
+                              items_b, n_items_b: int, n_users: int, n: int,
+                              *, score: str = "llr",
+                              exclude_self: bool = False):
+    """Plain torch reference: sparse A^T B in fp64, LLR in fp64 by the
+    formula of the module docstring rounded to fp32 (or the counts),
+    packed keys sorted, scattered into [Na, n]. Any n >= 1. Memory grows
+    with the number of distinct co-occurring pairs."""
     n = int(n)
     if n < 1:
         raise ValueError(f"n must be >= 1, got {n}")
-    u_indptr, u_items, _, _ = build_csrs(users, items, n_users, n_items)
-    dev = u_items.device
-    n_users, n_items = int(n_users), int(n_items)
-    top_ids = torch.full((n_items, n), -1, dtype=torch.int32, device=dev)
-    top_cnt = torch.zeros((n_items, n), dtype=torch.int32, device=dev)
-    if u_items.numel() == 0:
-        return top_ids, top_cnt
-    u = torch.repeat_interleave(torch.arange(n_users, device=dev),
-                                u_indptr[1:] - u_indptr[:-1])
-    A = torch.sparse_coo_tensor(
-        torch.stack([u, u_items.long()]),
-        torch.ones(u.numel(), dtype=torch.float64, device=dev),
-        (n_users, n_items)).coalesce()
+    llr = _check_score(score)
+    n_users, na, nb = int(n_users), int(n_items_a), int(n_items_b)
+    if exclude_self and na != nb:
+        raise ValueError("exclude_self needs n_items_a == n_items_b")
+    mats, degs = [], []
+    for users, items, size in ((users_a, items_a, na), (users_b, items_b, nb)):
+        if mats and users is users_a and items is items_a and size == na:
+            mats.append(mats[0])   # self mode: one pair set, built once
+            degs.append(degs[0])
+            break
+        u_indptr, u_items, i_indptr, _ = build_csrs(users, items, n_users,
+                                                    size)
+        dev = u_items.device
+        u = torch.repeat_interleave(torch.arange(n_users, device=dev),
+                                    u_indptr[1:] - u_indptr[:-1])
+        mats.append(torch.sparse_coo_tensor(
+            torch.stack([u, u_items.long()]),
+            torch.ones(u.numel(), dtype=torch.float64, device=dev),
+            (n_users, size)).coalesce())
+        degs.append(i_indptr[1:] - i_indptr[:-1])
+    top_ids = torch.full((na, n), -1, dtype=torch.int32, device=dev)
+    top_val = torch.zeros((na, n), device=dev,
+                          dtype=torch.float32 if llr else torch.int32)
+    if mats[0]._nnz() == 0 or mats[1]._nnz() == 0:
+        return top_ids, top_val
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", UserWarning)
-        C = torch.sparse.mm(A.t(), A).coalesce()
+        C = torch.sparse.mm(mats[0].t(), mats[1]).coalesce()
     ii, jj = C.indices()[0], C.indices()[1]
     vv = C.values().round().to(torch.int64)
-    off = (ii != jj) & (vv > 0)
-    ii, jj, vv = ii[off], jj[off], vv[off]
-    key = (vv << 32) | (0xFFFFFFFF - jj)
+    keep = vv > 0
+    if exclude_self:
+        keep &= ii != jj
+    ii, jj, vv = ii[keep], jj[keep], vv[keep]
+    if llr:
+        ai, bj = degs[0][ii], degs[1][jj]
+        s = (_xlx(torch.tensor(n_users)) - _xlx(ai) - _xlx(n_users - ai)
+             - _xlx(bj) - _xlx(n_users - bj) + _xlx(vv) + _xlx(ai - vv)
+             + _xlx(bj - vv) + _xlx(n_users - ai - bj + vv))
+        val = torch.clamp(2.0 * s, min=0.0).to(torch.float32)
+        hi = val.view(torch.int32).to(torch.int64)
+    else:
+        val = vv.to(torch.int32)
+        hi = vv
+    key = (hi << 32) | (0xFFFFFFFF - jj)
     o1 = torch.argsort(key, descending=True, stable=True)
     o2 = torch.argsort(ii[o1], stable=True)
     order = o1[o2]
-    ii, jj, vv = ii[order], jj[order], vv[order]
-    start = torch.zeros(n_items + 1, dtype=torch.int64, device=dev)
-    start[1:] = torch.bincount(ii, minlength=n_items).cumsum(0)
+    ii, jj, val = ii[order], jj[order], val[order]
+    start = torch.zeros(na + 1, dtype=torch.int64, device=dev)
+    start[1:] = torch.bincount(ii, minlength=na).cumsum(0)
     rank = torch.arange(ii.numel(), device=dev) - start[ii]
     keep = rank < n
     top_ids[ii[keep], rank[keep]] = jj[keep].to(torch.int32)
-    top_cnt[ii[keep], rank[keep]] = vv[keep].to(torch.int32)
-    return top_ids, top_cnt
+    top_val[ii[keep], rank[keep]] = val[keep]
+    return top_ids, top_val
+
+
+def cooccurrence_topn_ref(users, items, n_users: int, n_items: int, n: int,
+                          *, score: str = "count"):
+    """The reference in self mode: A^T A with the diagonal dropped."""
+    return cross_occurrence_topn_ref(users, items, n_items, users, items,
+                                     n_items, n_users, n, score=score,
+                                     exclude_self=True)
 
 
 def _check_csr(indptr, indices, n_cols: int, name: str):
@@ -164,11 +251,82 @@ def _check_csr(indptr, indices, n_cols: int, name: str):
                              f" vs {n_cols}")
 
 
+def _topn_tiers(u_indptr, u_items, i_indptr, i_users, n_cols: int, n: int,
+                llr: bool, exclude_self: bool, same_pairs: bool, col_deg,
+                hash_caps, pool, pool_slots, dense_lds):
+    """Validate, plan and launch every tier: rows from the item-major
+    CSR (i_indptr, i_users) of A, columns from the user-major CSR
+    (u_indptr, u_items) of B over n_cols items. col_deg: int64 [n_cols]
+    user counts of B's items (LLR only)."""
+    n_users = u_indptr.numel() - 1
+    n_rows = i_indptr.numel() - 1
+    if max(n_users, n_rows, n_cols) >= 2 ** 31:
+        raise ValueError("user and item counts must be below 2^31")
+    if exclude_self and n_rows != n_cols:
+        raise ValueError("exclude_self needs the same item count on both "
+                         "sides")
+    caps = HASH_CAPS if hash_caps is None else tuple(int(c) for c in hash_caps)
+    if len(caps) != 2 or caps[0] > HASH_CAPS[0] or caps[1] > HASH_CAPS[1]:
+        raise ValueError(f"hash_caps must be a pair within {HASH_CAPS}")
+    # a bad id is an out-of-bounds atomic: check before any launch
+    _check_csr(u_indptr, u_items, n_cols, "user-major CSR")
+    _check_csr(i_indptr, i_users, n_users, "item-major CSR")
+    if dense_lds is None:
+        dense_lds = (DENSE_LDS_MAX > 0 and n_cols <= DENSE_LDS_MAX
+                     and pool is None and pool_slots is None)
+    elif dense_lds and n_cols > DENSE_LDS_MAX:
+        raise ValueError(f"dense_lds needs N <= {DENSE_LDS_MAX}")
+    if pool is not None and (
+            pool.dtype != torch.int32 or pool.dim() != 2 or not pool.is_cuda
+            or not pool.is_contiguous() or pool.shape[0] < 1
+            or pool.shape[1] != n_cols):
+        raise ValueError("pool must be a contiguous int32 [G >= 1, N] "
+                         "GPU tensor")
+
+    from predictionio_amd.ops import hip_ext
+    ext = hip_ext()
+    dev = u_indptr.device
+    u_indptr, u_items = u_indptr.contiguous(), u_items.contiguous()
+    i_indptr, i_users = i_indptr.contiguous(), i_users.contiguous()
+    top_ids = torch.full((n_rows, n), -1, dtype=torch.int32, device=dev)
+    top_val = torch.zeros((n_rows, n), device=dev,
+                          dtype=torch.float32 if llr else torch.int32)
+    col_h = None
+    if llr:
+        col_h = _xlx(col_deg) + _xlx(n_users - col_deg)
+        col_deg = col_deg.to(torch.int32)
+    tiers = cooccurrence_plan(u_indptr, i_indptr, i_users, n_cols, caps,
+                              exclude_self=exclude_self,
+                              cross=not same_pairs)
+    for tier, rows in enumerate(tiers):
+        if rows.numel() == 0:
+            continue
+        tier_pool = None
+        if tier == 2 and dense_lds:
+            tier = 3
+        elif tier == 2:
+            slots = (int(pool_slots) if pool_slots is not None
+                     else _default_pool_bytes() // (4 * n_cols))
+            if pool is not None:
+                slots = min(slots, pool.shape[0])
+            slots = max(1, min(slots, rows.numel()))
+            tier_pool = (pool[:slots] if pool is not None else
+                         torch.zeros((slots, n_cols), dtype=torch.int32,
+                                     device=dev))
+        ext.cooc_topn(u_indptr, u_items, i_indptr, i_users, rows.contiguous(),
+                      n, tier, tier_pool, top_ids, top_val, llr=llr,
+                      exclude_self=exclude_self,
+                      n_cols=-1 if same_pairs else n_cols,
+                      col_deg=col_deg if llr else None, col_h=col_h)
+    return top_ids, top_val
+
+
 def cooccurrence_topn_csr(u_indptr, u_items, i_indptr, i_users, n: int, *,
-                          hash_caps=None, pool=None, pool_slots=None,
-                          dense_lds=None):
+                          score: str = "count", hash_caps=None, pool=None,
+                          pool_slots=None, dense_lds=None):
     """GPU entry on prebuilt CSRs (see build_csrs); returns (top_ids,
-    top_cnt), int32 [N, n].
+    top_cnt), int32 [N, n], or with score="llr" (top_ids, top_score
+    float32).
 
     The keyword arguments let tests reach every tier at tiny shapes:
     hash_caps lowers the routing caps (never above HASH_CAPS); pool is a
@@ -178,74 +336,90 @@ def cooccurrence_topn_csr(u_indptr, u_items, i_indptr, i_users, n: int, *,
     False: the global pool, None: LDS when it fits and no pool was
     asked for."""
     n = _check_n(n)
+    llr = _check_score(score)
     if not u_indptr.is_cuda:
         raise ValueError("cooccurrence_topn_csr needs GPU tensors")
-    n_users = u_indptr.numel() - 1
-    n_items = i_indptr.numel() - 1
-    if n_users >= 2 ** 31 or n_items >= 2 ** 31:
-        raise ValueError("user and item counts must be below 2^31")
-    caps = HASH_CAPS if hash_caps is None else tuple(int(c) for c in hash_caps)
-    if len(caps) != 2 or caps[0] > HASH_CAPS[0] or caps[1] > HASH_CAPS[1]:
-        raise ValueError(f"hash_caps must be a pair within {HASH_CAPS}")
     if u_items.numel() != i_users.numel():
         raise ValueError("the two CSRs must hold the same pairs")
-    # a bad id is an out-of-bounds atomic: check before any launch
-    _check_csr(u_indptr, u_items, n_items, "user-major CSR")
-    _check_csr(i_indptr, i_users, n_users, "item-major CSR")
-    if dense_lds is None:
-        dense_lds = (DENSE_LDS_MAX > 0 and n_items <= DENSE_LDS_MAX
-                     and pool is None and pool_slots is None)
-    elif dense_lds and n_items > DENSE_LDS_MAX:
-        raise ValueError(f"dense_lds needs N <= {DENSE_LDS_MAX}")
-    if pool is not None and (
-            pool.dtype != torch.int32 or pool.dim() != 2 or not pool.is_cuda
-            or not pool.is_contiguous() or pool.shape[0] < 1
-            or pool.shape[1] != n_items):
-        raise ValueError("pool must be a contiguous int32 [G >= 1, N] "
-                         "GPU tensor")
+    return _topn_tiers(u_indptr, u_items, i_indptr, i_users,
+                       i_indptr.numel() - 1, n, llr, True, True,
+                       i_indptr[1:] - i_indptr[:-1], hash_caps, pool,
+                       pool_slots, dense_lds)
 
-    from predictionio_amd.ops import hip_ext
-    ext = hip_ext()
-    dev = u_indptr.device
-    u_indptr, u_items = u_indptr.contiguous(), u_items.contiguous()
-    i_indptr, i_users = i_indptr.contiguous(), i_users.contiguous()
-    top_ids = torch.full((n_items, n), -1, dtype=torch.int32, device=dev)
-    top_cnt = torch.zeros((n_items, n), dtype=torch.int32, device=dev)
-    tiers = cooccurrence_plan(u_indptr, i_indptr, i_users, n_items, caps)
-    for tier, rows in enumerate(tiers):
-        if rows.numel() == 0:
-            continue
-        tier_pool = None
-        if tier == 2 and dense_lds:
-            tier = 3
-        elif tier == 2:
-            slots = (int(pool_slots) if pool_slots is not None
-                     else _default_pool_bytes() // (4 * n_items))
-            if pool is not None:
-                slots = min(slots, pool.shape[0])
-            slots = max(1, min(slots, rows.numel()))
-            tier_pool = (pool[:slots] if pool is not None else
-                         torch.zeros((slots, n_items), dtype=torch.int32,
-                                     device=dev))
-        ext.cooc_topn(u_indptr, u_items, i_indptr, i_users, rows.contiguous(),
-                      n, tier, tier_pool, top_ids, top_cnt)
-    return top_ids, top_cnt
+
+def cross_occurrence_topn_csr(csrs_a, csrs_b, n: int, *, score: str = "llr",
+                              exclude_self: bool = False, hash_caps=None,
+                              pool=None, pool_slots=None, dense_lds=None):
+    """GPU entry on the two pair sets' prebuilt CSRs (each the 4-tuple
+    of build_csrs, over the same users); returns (top_ids, top_score
+    float32) or, with score="count", (top_ids, top_cnt int32), [Na, n].
+    Rows walk A's item-major and B's user-major CSR; the pool, the LDS
+    counters and dense_lds are sized by Nb. The other keyword arguments
+    are those of cooccurrence_topn_csr."""
+    n = _check_n(n)
+    llr = _check_score(score)
+    _, _, a_indptr, a_users = csrs_a
+    b_indptr, b_items, bi_indptr, bi_users = csrs_b
+    if not (a_indptr.is_cuda and b_indptr.is_cuda):
+        raise ValueError("cross_occurrence_topn_csr needs GPU tensors")
+    if csrs_a[0].numel() != b_indptr.numel():
+        raise ValueError("the two pair sets must be over the same users")
+    # col_deg comes from B's item-major side: it must be B's pairs too
+    _check_csr(bi_indptr, bi_users, b_indptr.numel() - 1, "B item-major CSR")
+    if bi_users.numel() != b_items.numel():
+        raise ValueError("B's two CSRs must hold the same pairs")
+    return _topn_tiers(b_indptr, b_items, a_indptr, a_users,
+                       bi_indptr.numel() - 1, n, llr, bool(exclude_self),
+                       False, bi_indptr[1:] - bi_indptr[:-1], hash_caps,
+                       pool, pool_slots, dense_lds)
+
+
+def _pool_knobs(pool_bytes, n_cols: int):
+    if pool_bytes is None:
+        return {}
+    return {"pool_slots": max(1, int(pool_bytes) // (4 * max(1, int(n_cols)))),
+            "dense_lds": int(n_cols) <= DENSE_LDS_MAX}
 
 
 def cooccurrence_topn(users, items, n_users: int, n_items: int, n: int, *,
-                      pool_bytes=None):
+                      score: str = "count", pool_bytes=None):
     """(top_ids, top_cnt), int32 [n_items, n] on the inputs' device, from
-    raw (user, item) id tensors; duplicate pairs count once. CPU tensors
-    go to the reference, GPU tensors to the kernels (n <= 64 there).
-    pool_bytes bounds the dense tier's global counter pool (default 1 GiB,
-    or PIO_COOC_POOL_MB)."""
+    raw (user, item) id tensors; duplicate pairs count once. With
+    score="llr" the rows are ranked by the log-likelihood ratio and the
+    result is (top_ids, top_score float32). CPU tensors go to the
+    reference, GPU tensors to the kernels (n <= 64 there). pool_bytes
+    bounds the dense tier's global counter pool (default 1 GiB, or
+    PIO_COOC_POOL_MB)."""
+    _check_score(score)
     if not users.is_cuda:
-        return cooccurrence_topn_ref(users, items, n_users, n_items, n)
+        return cooccurrence_topn_ref(users, items, n_users, n_items, n,
+                                     score=score)
     n = _check_n(n)
     csrs = build_csrs(users, items, n_users, n_items)
-    slots = None
-    if pool_bytes is not None:
-        slots = max(1, int(pool_bytes) // (4 * max(1, int(n_items))))
-    return cooccurrence_topn_csr(*csrs, n, pool_slots=slots,
-                                 dense_lds=None if slots is None else
-                                 int(n_items) <= DENSE_LDS_MAX)
+    return cooccurrence_topn_csr(*csrs, n, score=score,
+                                 **_pool_knobs(pool_bytes, n_items))
+
+
+def cross_occurrence_topn(users_a, items_a, n_items_a: int, users_b, items_b,
+                          n_items_b: int, n_users: int, n: int, *,
+                          score: str = "llr", exclude_self: bool = False,
+                          pool_bytes=None):
+    """Cross-occurrence top-N of the pair sets A (rows) and B (columns)
+    over the same n_users users: (top_ids int32, top_score float32)
+    [n_items_a, n], or int32 counts with score="count"; see the module
+    docstring. CPU tensors go to cross_occurrence_topn_ref, GPU tensors
+    to the kernels (n <= 64 there)."""
+    _check_score(score)
+    if exclude_self and int(n_items_a) != int(n_items_b):
+        raise ValueError("exclude_self needs n_items_a == n_items_b")
+    if users_a.is_cuda != users_b.is_cuda:
+        raise ValueError("both pair sets must be on the same device")
+    if not users_a.is_cuda:
+        return cross_occurrence_topn_ref(
+            users_a, items_a, n_items_a, users_b, items_b, n_items_b,
+            n_users, n, score=score, exclude_self=exclude_self)
+    n = _check_n(n)
+    return cross_occurrence_topn_csr(
+        build_csrs(users_a, items_a, n_users, n_items_a),
+        build_csrs(users_b, items_b, n_users, n_items_b), n, score=score,
+        exclude_self=exclude_self, **_pool_knobs(pool_bytes, n_items_b))

@@ -54,7 +54,8 @@ extern "C" void launch_als_loss(
 extern "C" void launch_cooc_topn(
     const long long* u_indptr, const int* u_items, const long long* i_indptr,
     const int* i_users, const int* rows, int n_rows, int n, int tier,
-    int* pool, long long n_items, int* top_ids, int* top_cnt, int grid,
+    int* pool, long long n_items, int* top_ids, void* top_val, int llr,
+    int cross, const int* col_deg, const double* col_h, int n_users, int grid,
     hipStream_t stream);
 
 extern "C" int cooc_dense_lds_max();
@@ -481,23 +482,31 @@ torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
 
 // One tier of co-occurrence top-N (see cooc_topn.hip): the item rows
 // listed in `rows` are counted, selected and written to top_ids/top_cnt
-// [N, n] in place; rows not listed are left alone. tier 0 / 1: the
+// [Na, n] in place; rows not listed are left alone. tier 0 / 1: the
 // 1024- / 8192-slot LDS hash tables; tier 2: dense counters in `pool`,
-// a zero [G, N] i32 tensor that is all zero again afterwards, one
+// a zero [G, Nb] i32 tensor that is all zero again afterwards, one
 // persistent workgroup per counter row; tier 3: dense counters in LDS,
-// N <= cooc_dense_lds_max(). Ids are trusted
-// (ops/cooccurrence.py range-checks both CSRs first).
+// Nb <= cooc_dense_lds_max(). (i_indptr, i_users) is the item-major CSR
+// of the row side A, (u_indptr, u_items) the user-major CSR of the
+// column side B over Nb = n_cols items; n_cols < 0 says that they hold
+// the same pairs (Nb = Na). exclude_self drops the pair (i, i) and needs
+// Na == Nb. With llr set the rows are ranked by the log-likelihood
+// ratio, top_cnt is fp32 and col_deg i32 [Nb] / col_h f64 [Nb] carry the
+// column totals. Ids are trusted (ops/cooccurrence.py range-checks the
+// CSRs first).
 void cooc_topn(torch::Tensor u_indptr, torch::Tensor u_items,
                torch::Tensor i_indptr, torch::Tensor i_users,
                torch::Tensor rows, int64_t n, int64_t tier,
                c10::optional<torch::Tensor> pool, torch::Tensor top_ids,
-               torch::Tensor top_cnt) {
+               torch::Tensor top_cnt, bool llr, bool exclude_self,
+               int64_t n_cols, c10::optional<torch::Tensor> col_deg,
+               c10::optional<torch::Tensor> col_h) {
   auto check = [](const torch::Tensor& t, torch::ScalarType st, int64_t dim,
                   const char* name) {
     TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st &&
                     t.dim() == dim,
-                name, " must be a contiguous ", dim, "-D ",
-                st == torch::kInt64 ? "i64" : "i32", " GPU tensor");
+                name, " must be a contiguous ", dim, "-D ", c10::toString(st),
+                " GPU tensor");
   };
   check(u_indptr, torch::kInt64, 1, "u_indptr");
   check(i_indptr, torch::kInt64, 1, "i_indptr");
@@ -505,24 +514,41 @@ void cooc_topn(torch::Tensor u_indptr, torch::Tensor u_items,
   check(i_users, torch::kInt32, 1, "i_users");
   check(rows, torch::kInt32, 1, "rows");
   check(top_ids, torch::kInt32, 2, "top_ids");
-  check(top_cnt, torch::kInt32, 2, "top_cnt");
+  check(top_cnt, llr ? torch::kFloat32 : torch::kInt32, 2, "top_cnt");
   TORCH_CHECK(u_indptr.size(0) >= 1 && i_indptr.size(0) >= 1,
               "indptr tensors must not be empty");
-  TORCH_CHECK(u_items.size(0) == i_users.size(0),
+  TORCH_CHECK(n_cols >= 0 || u_items.size(0) == i_users.size(0),
               "the two CSRs must hold the same pairs");
   TORCH_CHECK(n >= 1 && n <= 64, "n must be in [1, 64], got ", n);
   TORCH_CHECK(tier >= 0 && tier <= 3, "tier must be 0, 1, 2 or 3");
-  const int64_t N = i_indptr.size(0) - 1;
-  TORCH_CHECK(N < (1LL << 31) && u_indptr.size(0) - 1 < (1LL << 31),
+  const int64_t Na = i_indptr.size(0) - 1;
+  const int64_t N = n_cols < 0 ? Na : n_cols;  // the counters' size
+  const int64_t U = u_indptr.size(0) - 1;
+  TORCH_CHECK(N < (1LL << 31) && Na < (1LL << 31) && U < (1LL << 31),
               "item and user counts must be below 2^31");
-  TORCH_CHECK(top_ids.size(0) == N && top_ids.size(1) == n &&
-                  top_cnt.size(0) == N && top_cnt.size(1) == n,
+  TORCH_CHECK(!exclude_self || N == Na,
+              "exclude_self needs the same item count on both sides");
+  TORCH_CHECK(top_ids.size(0) == Na && top_ids.size(1) == n &&
+                  top_cnt.size(0) == Na && top_cnt.size(1) == n,
               "top_ids and top_cnt must be [N, n]");
   const auto dev = u_indptr.device();
   TORCH_CHECK(u_items.device() == dev && i_indptr.device() == dev &&
                   i_users.device() == dev && rows.device() == dev &&
                   top_ids.device() == dev && top_cnt.device() == dev,
               "all tensors must be on one device");
+  const int* deg_ptr = nullptr;
+  const double* h_ptr = nullptr;
+  if (llr) {
+    TORCH_CHECK(col_deg.has_value() && col_h.has_value(),
+                "llr needs col_deg and col_h");
+    check(*col_deg, torch::kInt32, 1, "col_deg");
+    check(*col_h, torch::kFloat64, 1, "col_h");
+    TORCH_CHECK(col_deg->size(0) == N && col_h->size(0) == N &&
+                    col_deg->device() == dev && col_h->device() == dev,
+                "col_deg and col_h must be [Nb] on the inputs' device");
+    deg_ptr = col_deg->data_ptr<int>();
+    h_ptr = col_h->data_ptr<double>();
+  }
   const int64_t n_rows = rows.size(0);
   TORCH_CHECK(n_rows < (1LL << 31), "too many rows for one launch");
   if (n_rows == 0) return;
@@ -554,7 +580,8 @@ void cooc_topn(torch::Tensor u_indptr, torch::Tensor u_items,
       reinterpret_cast<const long long*>(i_indptr.data_ptr<int64_t>()),
       i_users.data_ptr<int>(), rows.data_ptr<int>(), (int)n_rows, (int)n,
       (int)tier, pool_ptr, (long long)N, top_ids.data_ptr<int>(),
-      top_cnt.data_ptr<int>(), (int)grid, stream);
+      top_cnt.data_ptr(), (int)llr, (int)!exclude_self, deg_ptr, h_ptr,
+      (int)U, (int)grid, stream);
   C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -678,7 +705,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Co-occurrence top-N of the listed item rows, one tier",
         py::arg("u_indptr"), py::arg("u_items"), py::arg("i_indptr"),
         py::arg("i_users"), py::arg("rows"), py::arg("n"), py::arg("tier"),
-        py::arg("pool"), py::arg("top_ids"), py::arg("top_cnt"));
+        py::arg("pool"), py::arg("top_ids"), py::arg("top_cnt"),
+        py::arg("llr") = false, py::arg("exclude_self") = true,
+        py::arg("n_cols") = -1, py::arg("col_deg") = py::none(),
+        py::arg("col_h") = py::none());
   m.def("topk_cand", &topk_cand,
         "Candidate-list top-K (or scores) over a list of segments",
         py::arg("Xq"), py::arg("Y"), py::arg("cand_indices"),

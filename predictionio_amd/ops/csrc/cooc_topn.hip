@@ -58,6 +58,39 @@
 // never among the n largest and dropping it loses nothing. The final
 // selection is the same routine.
 //
+// Variants (template parameters SCORE and CROSS, every new line a
+// compile-time branch: the <THREADS, T> count kernels are unchanged).
+//
+// Cross-occurrence: the row's users come from the item-major CSR of a
+// pair set A (Na row items), each user's items from the user-major CSR
+// of a second pair set B over the same users (Nb column items):
+// c[i][j] = |usersA(i) ∩ usersB(j)|. The counters are sized by Nb.
+// CROSS drops the j != i compare (ids of A and B are then unrelated);
+// A = B with the compare kept is the self mode above.
+//
+// SCORE = CO_LLR ranks by Dunning's log-likelihood ratio of the 2x2
+// table (k11 = c, k12 = Ai - c, k21 = Bj - c, k22 = U - Ai - Bj + c),
+//   llr = max(0, 2 (R_i - H_j + xlx(k11) + xlx(k12) + xlx(k21) + xlx(k22)))
+//   xlx(x) = x ln x,  R_i = xlx(U) - xlx(Ai) - xlx(U - Ai),
+//   H_j = xlx(Bj) + xlx(U - Bj)  (col_h, built once by the wrapper),
+// summed in fp64 (the terms reach U ln U and cancel to order 1) and
+// rounded to fp32 once; llr >= 0, so its fp32 bits order like the value
+// and the key is (bits(llr) << 32) | (0xFFFFFFFF - j): never 0, distinct
+// per j, and the selection below is used as it stands.
+//
+// The score needs Bj and H_j, two gathers that depend on j, and four
+// fp64 logarithms. Done inside the harvest they would sit on its chain
+// (slot -> j -> gather -> log) and run with most lanes off: an empty
+// hash slot or a dense visit that read c == 0 has nothing to score. So
+// in LLR mode the harvest appends the raw pair (c << 32) | j, unfiltered
+// (at most S per step, as before), and a score pass at the end of the
+// step rewrites buf[scored..L) in place: consecutive lanes take
+// consecutive entries, every lane has work, and the loop is software
+// pipelined by one entry - the two gathers of a lane's next entry are
+// issued before the logarithms of its current one. An entry whose key
+// is <= thr becomes 0, which co_compact never selects. Each lane owns
+// its entries, so the pass needs one barrier after it and no atomics.
+//
 // Ids are trusted: the Python wrapper range-checks both CSRs before the
 // launch (a bad id would be an out-of-bounds atomic).
 
@@ -68,6 +101,8 @@
 #define CO_NMAX 64          // largest n
 #define CO_GROUP 16         // lanes per user
 #define CO_DENSE_LDS 28672  // largest N whose dense counters fit in LDS
+#define CO_COUNT 0          // SCORE: rank by the count
+#define CO_LLR 1            // SCORE: rank by the log-likelihood ratio
 
 typedef unsigned long long co_u64;
 
@@ -78,8 +113,13 @@ struct CoSel {
   int len;         // keys in buf
 };
 
+// What the harvest appends: the final key, or in LLR mode the raw pair
+// that co_score turns into one.
+template <int SCORE>
 __device__ __forceinline__ co_u64 co_pack(int c, int j)
 {
+  if constexpr (SCORE == CO_LLR)
+    return ((co_u64)(unsigned)c << 32) | (co_u64)(unsigned)j;
   return ((co_u64)(unsigned)c << 32) | (co_u64)(0xFFFFFFFFu - (unsigned)j);
 }
 
@@ -94,8 +134,9 @@ __device__ __forceinline__ void co_append(CoSel& sel, co_u64 key, co_u64 thr)
 // The n largest of buf[0..L) to buf[0..min(n, L)), descending; len and
 // (when n were found) thr updated. Every thread calls it with the same L
 // after a barrier that follows the last append; ends on a barrier.
+// Returns the new length, the same value in every thread.
 template <int THREADS>
-__device__ void co_compact(CoSel& sel, int L, int n)
+__device__ int co_compact(CoSel& sel, int L, int n)
 {
   const int tid = threadIdx.x;
   if (tid == 0) sel.best[0] = 0;
@@ -124,17 +165,84 @@ __device__ void co_compact(CoSel& sel, int L, int n)
     if (r == n) sel.thr = sel.buf[n - 1];
   }
   __syncthreads();
+  return r;
 }
 
-// End of a harvest step that appended at most S keys.
+// The row's side of the LLR: everything the score of (i, j) needs that
+// does not depend on j.
+struct CoLlr {
+  const int* __restrict__ col_deg;    // [Nb] Bj
+  const double* __restrict__ col_h;   // [Nb] H_j
+  double r;                           // R_i
+  int a, u;                           // Ai, U
+};
+
+__device__ __forceinline__ double co_xlx(int x)
+{
+  return x > 0 ? (double)x * log((double)x) : 0.0;
+}
+
+// buf[lo..L): raw pairs (c << 32) | j to keys, in place; <= thr to 0.
+// Entries lo + tid, + THREADS, ... belong to this thread. The gathers of
+// entry k + THREADS are in flight while entry k is scored.
 template <int THREADS>
+__device__ __forceinline__ void co_score(CoSel& sel, int lo, int L,
+                                         const CoLlr& m)
+{
+  const co_u64 thr = sel.thr;
+  int k = lo + (int)threadIdx.x;
+  co_u64 e = 0;
+  int bj = 0;
+  double h = 0.0;
+  if (k < L) {
+    e = sel.buf[k];
+    bj = m.col_deg[(unsigned)e];
+    h = m.col_h[(unsigned)e];
+  }
+  while (k < L) {
+    const int kn = k + THREADS;
+    co_u64 en = 0;
+    int bjn = 0;
+    double hn = 0.0;
+    if (kn < L) {
+      en = sel.buf[kn];
+      bjn = m.col_deg[(unsigned)en];
+      hn = m.col_h[(unsigned)en];
+    }
+    const int c = (int)(e >> 32);
+    const double s = (m.r - h) + co_xlx(c) + co_xlx(m.a - c) +
+                     co_xlx(bj - c) + co_xlx(m.u - m.a - bj + c);
+    const float llr = (float)fmax(0.0, 2.0 * s);
+    const co_u64 key = ((co_u64)__float_as_uint(llr) << 32) |
+                       (co_u64)(0xFFFFFFFFu - (unsigned)e);
+    sel.buf[k] = key > thr ? key : 0;
+    k = kn;
+    e = en;
+    bj = bjn;
+    h = hn;
+  }
+}
+
+// End of a harvest step that appended at most S keys. LLR mode: the
+// step's raw pairs are buf[scored..L); `scored` follows the length.
+template <int THREADS, int SCORE>
 __device__ __forceinline__ void co_step_end(CoSel& sel, int n, int S,
-                                            bool final)
+                                            bool final, int& scored,
+                                            const CoLlr& m)
 {
   __syncthreads();
   const int L = sel.len;
   __syncthreads();  // everyone holds L before anyone appends again
-  if (final || L > CO_SELECT_BUF - S) co_compact<THREADS>(sel, L, n);
+  if constexpr (SCORE == CO_LLR) {
+    co_score<THREADS>(sel, scored, L, m);
+    scored = L;
+    __syncthreads();
+  }
+  if (final || L > CO_SELECT_BUF - S) {
+    // from the register: the next step's appends already add to sel.len
+    const int len = co_compact<THREADS>(sel, L, n);
+    if constexpr (SCORE == CO_LLR) scored = len;
+  }
 }
 
 // A 16-lane group's resumable walk over (user of the row, item of the
@@ -157,8 +265,9 @@ __device__ __forceinline__ void co_walk_init(
 }
 
 // Up to `quota` group iterations, each calling f(j) for at most one item
-// j != self per lane. Returns true when the group's share is finished.
-template <int NG, class F>
+// per lane (EXCL: j != self). Returns true when the group's share is
+// finished.
+template <int NG, bool EXCL, class F>
 __device__ __forceinline__ bool co_walk(
     CoWalk& w, const long long* __restrict__ u_indptr,
     const int* __restrict__ u_items, const int* __restrict__ i_users,
@@ -178,7 +287,7 @@ __device__ __forceinline__ bool co_walk(
     const long long qq = w.q + sub;
     if (qq < w.e) {
       const int j = u_items[qq];
-      if (j != self) f(j);
+      if (!EXCL || j != self) f(j);
     }
     w.q += CO_GROUP;
     --quota;
@@ -186,19 +295,22 @@ __device__ __forceinline__ bool co_walk(
   return w.q >= w.e && w.un < 0;
 }
 
-template <int THREADS, int T>
+template <int THREADS, int T, int SCORE = CO_COUNT, bool CROSS = false>
 __global__ __launch_bounds__(THREADS)
 void cooc_kernel(
-    const long long* __restrict__ u_indptr,  // U + 1
+    const long long* __restrict__ u_indptr,  // U + 1        (B)
     const int* __restrict__ u_items,         // nnz, user-major
-    const long long* __restrict__ i_indptr,  // N + 1
+    const long long* __restrict__ i_indptr,  // Na + 1       (A)
     const int* __restrict__ i_users,         // nnz, item-major
     const int* __restrict__ rows,            // n_rows item ids, heavy first
     int n_rows, int n,
-    int* __restrict__ pool,                  // T == 0: [gridDim.x, N] zeros
-    long long n_items,
-    int* __restrict__ top_ids,               // [N, n]
-    int* __restrict__ top_cnt)               // [N, n]
+    int* __restrict__ pool,                  // T == 0: [gridDim.x, Nb] zeros
+    long long n_items,                       // Nb, the counters' size
+    int* __restrict__ top_ids,               // [Na, n]
+    int* __restrict__ top_cnt,               // [Na, n]; LLR: fp32 bits
+    const int* __restrict__ col_deg,         // LLR: [Nb] users of column j
+    const double* __restrict__ col_h,        // LLR: [Nb] H_j
+    int n_users)                             // LLR: U
 {
   constexpr int NG = THREADS / CO_GROUP;
   constexpr int K = (CO_SELECT_BUF - CO_NMAX) / THREADS;
@@ -238,12 +350,21 @@ void cooc_kernel(
       sel.len = 0;
       sel.thr = 0;
     }
+    CoLlr m{};
+    int scored = 0;
+    if constexpr (SCORE == CO_LLR) {
+      m.col_deg = col_deg;
+      m.col_h = col_h;
+      m.a = (int)(uend - ustart);
+      m.u = n_users;
+      m.r = co_xlx(m.u) - co_xlx(m.a) - co_xlx(m.u - m.a);
+    }
 
     // ---- count
     CoWalk w;
     co_walk_init<NG>(w, i_users, ustart, uend, grp);
-    co_walk<NG>(w, u_indptr, u_items, i_users, self, sub, 0x7fffffff,
-                [&](int j) {
+    co_walk<NG, !CROSS>(w, u_indptr, u_items, i_users, self, sub, 0x7fffffff,
+                        [&](int j) {
       if constexpr (T > 0) {
         unsigned h = ((unsigned)j * 0x9E3779B1u) >> (32 - __builtin_ctz(TS));
         for (int p = 0; p < T; ++p) {
@@ -267,7 +388,7 @@ void cooc_kernel(
     // ---- harvest and select
     if constexpr (T > 0) {
       for (int base = 0; base < T; base += S) {
-        const co_u64 thr = sel.thr;
+        const co_u64 thr = SCORE == CO_LLR ? 0 : sel.thr;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           const int s = base + k * THREADS + tid;
@@ -277,25 +398,25 @@ void cooc_kernel(
               const int c = cnts[s];
               keys[s] = -1;  // the table is empty again for the next row
               cnts[s] = 0;
-              co_append(sel, co_pack(c, j), thr);
+              co_append(sel, co_pack<SCORE>(c, j), thr);
             }
           }
         }
-        co_step_end<THREADS>(sel, n, S, base + S >= T);
+        co_step_end<THREADS, SCORE>(sel, n, S, base + S >= T, scored, m);
       }
     } else {
       co_walk_init<NG>(w, i_users, ustart, uend, grp);
       for (;;) {
-        const co_u64 thr = sel.thr;
-        const bool done = co_walk<NG>(
+        const co_u64 thr = SCORE == CO_LLR ? 0 : sel.thr;
+        const bool done = co_walk<NG, !CROSS>(
             w, u_indptr, u_items, i_users, self, sub, K, [&](int j) {
               int c;
               if constexpr (T == 0) c = atomicExch(&gcnt[j], 0);
               else c = atomicExch(&dcnt[j], 0);
-              if (c != 0) co_append(sel, co_pack(c, j), thr);
+              if (c != 0) co_append(sel, co_pack<SCORE>(c, j), thr);
             });
         const int pending = __syncthreads_or(!done);
-        co_step_end<THREADS>(sel, n, S, !pending);
+        co_step_end<THREADS, SCORE>(sel, n, S, !pending, scored, m);
         if (!pending) break;
       }
     }
@@ -315,33 +436,58 @@ void cooc_kernel(
 // tier 0: <64, 1024>, tier 1: <256, 8192>, tier 2: dense over `pool`
 // (grid = its counter rows), tier 3: dense in LDS (n_items <=
 // CO_DENSE_LDS). The caller sizes the grid.
+template <int SCORE, bool CROSS>
+static void co_launch(
+    const long long* u_indptr, const int* u_items, const long long* i_indptr,
+    const int* i_users, const int* rows, int n_rows, int n, int tier,
+    int* pool, long long n_items, int* top_ids, int* top_val,
+    const int* col_deg, const double* col_h, int n_users, int grid,
+    hipStream_t stream)
+{
+  if (tier == 0)
+    hipLaunchKernelGGL((cooc_kernel<64, 1024, SCORE, CROSS>),
+                       dim3((unsigned)grid), dim3(64), 0, stream, u_indptr,
+                       u_items, i_indptr, i_users, rows, n_rows, n, pool,
+                       n_items, top_ids, top_val, col_deg, col_h, n_users);
+  else if (tier == 1)
+    hipLaunchKernelGGL((cooc_kernel<256, 8192, SCORE, CROSS>),
+                       dim3((unsigned)grid), dim3(256), 0, stream, u_indptr,
+                       u_items, i_indptr, i_users, rows, n_rows, n, pool,
+                       n_items, top_ids, top_val, col_deg, col_h, n_users);
+  else if (tier == 2)
+    hipLaunchKernelGGL((cooc_kernel<256, 0, SCORE, CROSS>),
+                       dim3((unsigned)grid), dim3(256), 0, stream, u_indptr,
+                       u_items, i_indptr, i_users, rows, n_rows, n, pool,
+                       n_items, top_ids, top_val, col_deg, col_h, n_users);
+  else if (n_items <= CO_DENSE_LDS)
+    hipLaunchKernelGGL((cooc_kernel<256, -1, SCORE, CROSS>),
+                       dim3((unsigned)grid), dim3(256), 0, stream, u_indptr,
+                       u_items, i_indptr, i_users, rows, n_rows, n, pool,
+                       n_items, top_ids, top_val, col_deg, col_h, n_users);
+}
+
+// (u_indptr, u_items): user-major CSR of the column side B, n_items = Nb;
+// (i_indptr, i_users): item-major CSR of the row side A. llr != 0 ranks
+// by LLR and writes fp32 scores to top_val (col_deg, col_h, n_users are
+// read only then); cross != 0 keeps the pair (i, i).
 extern "C" void launch_cooc_topn(
     const long long* u_indptr, const int* u_items, const long long* i_indptr,
     const int* i_users, const int* rows, int n_rows, int n, int tier,
-    int* pool, long long n_items, int* top_ids, int* top_cnt, int grid,
+    int* pool, long long n_items, int* top_ids, void* top_val, int llr,
+    int cross, const int* col_deg, const double* col_h, int n_users, int grid,
     hipStream_t stream)
 {
   if (n_rows <= 0 || grid <= 0) return;
-  if (tier == 0)
-    hipLaunchKernelGGL((cooc_kernel<64, 1024>), dim3((unsigned)grid),
-                       dim3(64), 0, stream, u_indptr, u_items, i_indptr,
-                       i_users, rows, n_rows, n, pool, n_items, top_ids,
-                       top_cnt);
-  else if (tier == 1)
-    hipLaunchKernelGGL((cooc_kernel<256, 8192>), dim3((unsigned)grid),
-                       dim3(256), 0, stream, u_indptr, u_items, i_indptr,
-                       i_users, rows, n_rows, n, pool, n_items, top_ids,
-                       top_cnt);
-  else if (tier == 2)
-    hipLaunchKernelGGL((cooc_kernel<256, 0>), dim3((unsigned)grid),
-                       dim3(256), 0, stream, u_indptr, u_items, i_indptr,
-                       i_users, rows, n_rows, n, pool, n_items, top_ids,
-                       top_cnt);
-  else if (n_items <= CO_DENSE_LDS)
-    hipLaunchKernelGGL((cooc_kernel<256, -1>), dim3((unsigned)grid),
-                       dim3(256), 0, stream, u_indptr, u_items, i_indptr,
-                       i_users, rows, n_rows, n, pool, n_items, top_ids,
-                       top_cnt);
+  int* const val = static_cast<int*>(top_val);
+#define CO_GO(SCORE, CROSS)                                                 \
+  co_launch<SCORE, CROSS>(u_indptr, u_items, i_indptr, i_users, rows,       \
+                          n_rows, n, tier, pool, n_items, top_ids, val,     \
+                          col_deg, col_h, n_users, grid, stream)
+  if (llr && cross) CO_GO(CO_LLR, true);
+  else if (llr) CO_GO(CO_LLR, false);
+  else if (cross) CO_GO(CO_COUNT, true);
+  else CO_GO(CO_COUNT, false);
+#undef CO_GO
 }
 
 extern "C" int cooc_dense_lds_max() { return CO_DENSE_LDS; }

@@ -50,6 +50,7 @@ class ViewEvent:
     user: str
     item: str
     t: float
+    name: str = "view"   # the event's name (DataSource eventNames)
 
 
 @dataclass
@@ -117,7 +118,7 @@ class DataSource(BaseDataSource):
                  event_store.aggregate_properties(app, "item").items()}
         views = [
             ViewEvent(e.entity_id, e.target_entity_id,
-                      e.event_time.timestamp())
+                      e.event_time.timestamp(), e.event)
             for e in event_store.find(app, entity_type="user",
                                       event_names=names,
                                       target_entity_type="item")
@@ -352,8 +353,9 @@ class CooccurrenceModel:
     def __init__(self, top_n: Dict[int, List[Tuple[int, int]]],
                  item_map: BiMap, items: Dict[str, Item],
                  top_ids=None, top_cnt=None):
-        self.top_n = top_n          # item → [(other_item, count)]
-        # the same lists as host numpy int32 [N, n]: id -1 / count 0 pad
+        self.top_n = top_n          # item → [(other_item, count or score)]
+        # the same lists as host numpy [N, n]: id -1 / count 0 pad; int32,
+        # the scores of scoring="llr" float32
         self.top_ids = top_ids
         self.top_cnt = top_cnt
         self.item_map = item_map
@@ -363,7 +365,12 @@ class CooccurrenceModel:
 
 class CooccurrenceAlgorithm(Algorithm):
     """Params: n (top co-occurrences kept per item)
-    (CooccurrenceAlgorithm.scala:49-108)."""
+    (CooccurrenceAlgorithm.scala:49-108); scoring, "count" (default) or
+    "llr" (log-likelihood ratio: a merely popular item scores near 0);
+    targetEvent, unset by default: when set, rows are counted over the
+    events named `event` (default: all read events), columns over the
+    targetEvent events ("viewed this, bought ..."), the item itself
+    excluded."""
 
     def train(self, pd: PreparedData) -> CooccurrenceModel:
         """Pair counting as a per-item top-N over c[i][j] = number of
@@ -372,7 +379,11 @@ class CooccurrenceAlgorithm(Algorithm):
         GPU the fused pair-count kernels (ops/cooccurrence.py) count each
         item row on chip and only the [N, n] result reaches the host; on
         CPU the same op runs its sparse A^T A reference."""
-        from predictionio_amd.ops.cooccurrence import cooccurrence_topn
+        from predictionio_amd.ops.cooccurrence import (
+            cooccurrence_topn, cross_occurrence_topn,
+        )
+        scoring = self.params.get("scoring", "count")
+        target = self.params.get("targetEvent")
         item_map = BiMap.string_int(
             [v.item for v in pd.view_events] + list(pd.items))
         user_map = BiMap.string_int(v.user for v in pd.view_events)
@@ -383,12 +394,26 @@ class CooccurrenceAlgorithm(Algorithm):
             return CooccurrenceModel({}, item_map, pd.items)
         device = (torch.device("cuda") if torch.cuda.is_available()
                   else torch.device("cpu"))
-        u = torch.tensor([user_map[v.user] for v in pd.view_events],
-                         dtype=torch.int64, device=device)
-        i = torch.tensor([item_map[v.item] for v in pd.view_events],
-                         dtype=torch.int64, device=device)
+
+        def pairs(events):
+            return (torch.tensor([user_map[v.user] for v in events],
+                                 dtype=torch.int64, device=device),
+                    torch.tensor([item_map[v.item] for v in events],
+                                 dtype=torch.int64, device=device))
+
         # user-distinct (view twice ≠ two pairs): the op dedups the pairs
-        ids, cnt = cooccurrence_topn(u, i, n_users, n_items, n_keep)
+        if target is None:
+            u, i = pairs(pd.view_events)
+            ids, cnt = cooccurrence_topn(u, i, n_users, n_items, n_keep,
+                                         score=scoring)
+        else:
+            source = self.params.get("event")
+            ua, ia = pairs([v for v in pd.view_events
+                            if source is None or v.name == source])
+            ub, ib = pairs([v for v in pd.view_events if v.name == target])
+            ids, cnt = cross_occurrence_topn(
+                ua, ia, n_items, ub, ib, n_items, n_users, n_keep,
+                score=scoring, exclude_self=True)
         top_ids, top_cnt = ids.cpu().numpy(), cnt.cpu().numpy()
         top_n: Dict[int, List[Tuple[int, int]]] = {}
         for it in (top_ids[:, 0] >= 0).nonzero()[0].tolist():
@@ -400,7 +425,7 @@ class CooccurrenceAlgorithm(Algorithm):
 
     def predict(self, model: CooccurrenceModel, query) -> PredictedResult:
         q = query if isinstance(query, Query) else Query.from_json(query)
-        counts: Dict[int, int] = defaultdict(int)
+        counts: Dict[int, float] = defaultdict(int)  # or summed scores
         qidx = {model.item_map.get(i) for i in q.items}
         for i in q.items:
             ii = model.item_map.get(i)
@@ -477,7 +502,7 @@ class FollowDataSource(BaseDataSource):
         app = self.params["appName"]
         follows = [
             ViewEvent(e.entity_id, e.target_entity_id,
-                      e.event_time.timestamp())
+                      e.event_time.timestamp(), e.event)
             for e in event_store.find(app, entity_type="user",
                                       event_names=["follow"],
                                       target_entity_type="user")

@@ -10,6 +10,16 @@ run only where that count is at most --old-max-triples.
 
     python scripts/cooccurrence_bench.py                 # every shape
     python scripts/cooccurrence_bench.py --shapes small  # one of them
+    python scripts/cooccurrence_bench.py --score both    # count and LLR
+    python scripts/cooccurrence_bench.py --cross --score llr
+
+--score both times the two scores alternating in one process (count,
+llr, count, ...), whole call and tier by tier, so their difference is the
+score stage and not drift between processes. --cross takes the rows from
+the shape's pair set and the columns from a second one over the same
+users and items with a quarter of the views ("viewed this, bought ...");
+its old path is the torch route, cross_occurrence_topn_ref on the device
+(sparse A^T B, then the LLR over its entries).
 
 Prints one JSON line per measurement: wall time, peak device memory
 above the inputs, and for the kernels the rows, summed pair visits and
@@ -39,10 +49,11 @@ RUNS = 7
 N_KEEP = 10
 
 
-def make_pairs(name, device):
+def make_pairs(name, device, seed=0, views_div=1):
     import torch
     n_users, n_items, views, dist = SHAPES[name]
-    g = torch.Generator(device=device).manual_seed(0)
+    views = max(1, views // views_div)
+    g = torch.Generator(device=device).manual_seed(seed)
     if dist == "uniform":
         i = torch.randint(0, n_items, (n_users, views), generator=g,
                           device=device)
@@ -57,17 +68,25 @@ def make_pairs(name, device):
     return u.reshape(-1).contiguous(), i.reshape(-1).contiguous()
 
 
-def timed(fn):
+def timed_each(fns):
+    """{name: median seconds} of the callables in `fns`, run alternating
+    (a, b, a, b, ...) after one warm-up each."""
     import torch
-    fn()  # warm-up
-    out = []
+    for fn in fns.values():
+        fn()  # warm-up
+    out = {k: [] for k in fns}
     for _ in range(RUNS):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append(time.perf_counter() - t)
-    return statistics.median(out)
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out[k].append(time.perf_counter() - t)
+    return {k: statistics.median(v) for k, v in out.items()}
+
+
+def timed(fn):
+    return timed_each({"": fn})[""]
 
 
 def old_path(u, i, n_users, n_items, n_keep):
@@ -90,40 +109,64 @@ def old_path(u, i, n_users, n_items, n_keep):
     return ii[order], jj[order], vv[order]
 
 
-def child(name, path, dense_lds):
+def child(name, path, dense_lds, scores, cross):
     import torch
     from predictionio_amd.ops import cooccurrence as co
     from predictionio_amd.ops import hip_ext
     dev = torch.device("cuda")
     n_users, n_items, _, _ = SHAPES[name]
     u, i = make_pairs(name, dev)
-    res = {"shape": name, "path": path, "users": n_users, "items": n_items,
-           "pairs": int(u.numel())}
+    ub, ib = make_pairs(name, dev, seed=1, views_div=4) if cross else (u, i)
+    res = {"shape": name, "path": path, "cross": cross, "users": n_users,
+           "items": n_items, "pairs": int(u.numel()),
+           "col_pairs": int(ub.numel())}
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     before = torch.cuda.memory_allocated()
-    if path == "old":
+    lds = {"auto": None, "lds": True, "pool": False}[dense_lds]
+
+    def whole(score):
+        a = co.build_csrs(u, i, n_users, n_items)
+        if not cross:
+            return co.cooccurrence_topn_csr(*a, N_KEEP, score=score,
+                                            dense_lds=lds)
+        return co.cross_occurrence_topn_csr(
+            a, co.build_csrs(ub, ib, n_users, n_items), N_KEEP, score=score,
+            dense_lds=lds)
+
+    if path == "old" and cross:
+        res["wall_s"] = timed_each({sc: (lambda sc=sc: (
+            co.cross_occurrence_topn_ref(u, i, n_items, ub, ib, n_items,
+                                         n_users, N_KEEP, score=sc)))
+            for sc in scores})
+    elif path == "old":
         res["wall_s"] = timed(lambda: old_path(u, i, n_users, n_items, N_KEEP))
     else:
-        lds = {"auto": None, "lds": True, "pool": False}[dense_lds]
-        csrs = co.build_csrs(u, i, n_users, n_items)
-        res["wall_s"] = timed(
-            lambda: co.cooccurrence_topn_csr(*co.build_csrs(
-                u, i, n_users, n_items), N_KEEP, dense_lds=lds))
+        res["wall_s"] = timed_each({sc: (lambda sc=sc: whole(sc))
+                                    for sc in scores})
     torch.cuda.synchronize()
     res["peak_mib"] = round(
         (torch.cuda.max_memory_allocated() - before) / 2 ** 20, 1)
     if path == "new":
-        # per tier: rows, pair visits, and the launch alone
+        # per tier: rows, pair visits, and the launch alone, per score
         ext = hip_ext()
-        u_indptr, u_items, i_indptr, i_users = csrs
-        tiers = co.cooccurrence_plan(u_indptr, i_indptr, i_users, n_items)
+        _, _, i_indptr, i_users = co.build_csrs(u, i, n_users, n_items)
+        u_indptr, u_items, c_indptr, _ = co.build_csrs(ub, ib, n_users,
+                                                       n_items)
+        tiers = co.cooccurrence_plan(u_indptr, i_indptr, i_users, n_items,
+                                     exclude_self=not cross, cross=cross)
         d = u_indptr[1:] - u_indptr[:-1]
         cs = torch.zeros(i_users.numel() + 1, dtype=torch.int64, device=dev)
         cs[1:] = d[i_users.long()].cumsum(0)
         work = cs[i_indptr[1:]] - cs[i_indptr[:-1]]
         ids = torch.full((n_items, N_KEEP), -1, dtype=torch.int32, device=dev)
-        cnt = torch.zeros_like(ids)
+        val = {"count": torch.zeros_like(ids),
+               "llr": torch.zeros(ids.shape, device=dev)}
+        col_deg = c_indptr[1:] - c_indptr[:-1]
+        col_h = (torch.xlogy(col_deg.double(), col_deg.double())
+                 + torch.xlogy((n_users - col_deg).double(),
+                               (n_users - col_deg).double()))
+        col_deg = col_deg.to(torch.int32)
         use_lds = n_items <= co.DENSE_LDS_MAX if lds is None else lds
         res["dense_in_lds"] = bool(use_lds)
         res["tiers"] = []
@@ -139,9 +182,11 @@ def child(name, path, dense_lds):
                                        (1 << 30) // (4 * n_items)))
                     pool = torch.zeros((slots, n_items), dtype=torch.int32,
                                        device=dev)
-                entry["s"] = timed(lambda: ext.cooc_topn(
+                entry["s"] = timed_each({sc: (lambda sc=sc: ext.cooc_topn(
                     u_indptr, u_items, i_indptr, i_users, rows, N_KEEP,
-                    tier, pool, ids, cnt))
+                    tier, pool, ids, val[sc], llr=sc == "llr",
+                    exclude_self=not cross, n_cols=n_items if cross else -1,
+                    col_deg=col_deg, col_h=col_h)) for sc in scores})
             res["tiers"].append(entry)
     print(json.dumps(res), flush=True)
 
@@ -154,15 +199,22 @@ def main():
     ap.add_argument("--old-max-triples", type=float, default=1e8)
     ap.add_argument("--dense", default="auto", choices=["auto", "lds", "pool"],
                     help="where rows above the hash caps keep counters")
+    ap.add_argument("--score", default="count",
+                    choices=["count", "llr", "both"])
+    ap.add_argument("--cross", action="store_true",
+                    help="columns from a second pair set")
     ap.add_argument("--child", nargs=2, metavar=("SHAPE", "PATH"))
     a = ap.parse_args()
+    scores = ["count", "llr"] if a.score == "both" else [a.score]
     if a.child:
-        child(a.child[0], a.child[1], a.dense)
+        child(a.child[0], a.child[1], a.dense, scores, a.cross)
         return 0
     for name in a.shapes.split(","):
         n_users, _, views, _ = SHAPES[name]
         paths = ["new"]
-        if n_users * views * views <= a.old_max_triples:
+        if not a.cross and scores != ["count"]:
+            pass  # the old self path has no LLR
+        elif n_users * views * views <= a.old_max_triples:
             paths.append("old")
         else:
             print(json.dumps({"shape": name, "path": "old",
@@ -170,7 +222,9 @@ def main():
                                          "--old-max-triples"}), flush=True)
         for path in paths:
             cmd = [sys.executable, os.path.abspath(__file__), "--child", name,
-                   path, "--dense", a.dense]
+                   path, "--dense", a.dense, "--score", a.score]
+            if a.cross:
+                cmd.append("--cross")
             try:
                 rc = subprocess.run(cmd, timeout=a.timeout).returncode
             except subprocess.TimeoutExpired:
