@@ -18,7 +18,7 @@ CSRC = os.path.join(OPS_DIR, "csrc")
 SO_PATH = os.path.join(OPS_DIR, "_pio_hip.so")
 SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
            "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
-           "cooc_topn.hip", "topk_cand.hip"]
+           "cooc_topn.hip", "topk_cand.hip", "indicator_topk.hip"]
 # compiled on their own with packed fp32 VALU ops off (the vectorizer may
 # otherwise pair independent fp32 chains), then linked with the rest.
 # cooc_topn.hip is here since its LLR score stage: today it holds no
@@ -26,7 +26,9 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
 # without the flag, count kernels included; the flag keeps a later score
 # functor's fp32 code (cosine, Jaccard) from being packed unnoticed. The
 # file includes only the HIP runtime, so it needs none of the torch -D's.
-NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip"]
+# indicator_topk.hip: its fp32 segment sums are an ordered chain of adds
+# (the canonical sum) and must stay one.
+NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip", "indicator_topk.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

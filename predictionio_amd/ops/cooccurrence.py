@@ -41,6 +41,10 @@ bits are order-preserving; the key is never 0 and distinct per j).
 Unused slots are id -1, score 0. The sum is formed in fp64 and rounded
 to fp32 once: the terms reach U ln U (1.4e7 at a million users) and
 cancel down to order 1, fp32 would keep no digits.
+
+Serving. indicator_topk (at the end of this module) answers a batch of
+queries from the [N, n] table these ops return: it sums the rows of each
+query's items, filters and ranks, on a GPU in csrc/indicator_topk.hip.
 """
 
 from __future__ import annotations
@@ -423,3 +427,321 @@ def cross_occurrence_topn(users_a, items_a, n_items_a: int, users_b, items_b,
         build_csrs(users_a, items_a, n_users, n_items_a),
         build_csrs(users_b, items_b, n_users, n_items_b), n, score=score,
         exclude_self=exclude_self, **_pool_knobs(pool_bytes, n_items_b))
+
+
+# --------------------------------------------------------------------------
+# Indicator top-K: serve the [Nr, n] table the ops above return.
+#
+#   s[b][j] = sum of top_scores[i][c] over the rows i of query b and the
+#             columns c with top_ids[i][c] == j
+#
+# Candidates of b are the j that occur at least once (a sum of 0 still
+# counts) and pass every filter given; the result is the K candidates with
+# the largest s, score descending then id ascending, padded with -1 / 0.
+# Count tables sum in int32, exactly. Float tables add the addends of one
+# (b, j) in ascending value order in fp32, one rounding per add: the
+# canonical sum, a function of the multiset of addends alone, so the
+# kernel (csrc/indicator_topk.hip) and indicator_topk_ref agree bit for
+# bit with each other and with themselves whatever the order of a table
+# row or of the threads.
+# --------------------------------------------------------------------------
+
+# entry counts (query rows x n) the two kernel instantiations take; larger
+# queries go through indicator_topk_ref
+IND_WAVE_MAX = 512
+IND_WG_MAX = 8192
+IND_K_MAX = 1024
+# table entries the torch route holds at a time
+IND_REF_CHUNK = 1 << 22
+
+
+def _check_lists(indptr, indices, B: int, n_cols: int, name: str):
+    """A per-query CSR of sorted id lists: int64 indptr of B + 1 from 0
+    to nnz, not decreasing; int32 ids in [0, n_cols), strictly ascending
+    inside every query."""
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise ValueError(f"{name}: indptr must be int64 and indices int32")
+    _check_csr(indptr, indices, n_cols, name)
+    if indptr.numel() != B + 1:
+        raise ValueError(f"{name}: indptr must have B + 1 = {B + 1} entries")
+    nnz = indices.numel()
+    if nnz > 1:
+        is_start = torch.zeros(nnz + 1, dtype=torch.bool,
+                               device=indices.device)
+        is_start[indptr] = True
+        if bool(((indices[1:] <= indices[:-1]) & ~is_start[1:nnz]).any()):
+            raise ValueError(f"{name}: ids must be strictly ascending inside"
+                             " every query (sorted, no duplicates)")
+
+
+def check_indicator_table(top_ids, top_scores, n_cols=None) -> None:
+    """The table contract of indicator_topk: top_ids int32 [Nr, n] in
+    [-1, n_cols), top_scores int32 or float32 of the same shape, every
+    score >= 0 and finite. A model checks its table once with this and
+    then calls indicator_topk(..., check_table=False)."""
+    if top_ids.dim() != 2 or top_ids.dtype != torch.int32:
+        raise ValueError("top_ids must be a 2-D int32 tensor")
+    if top_scores.shape != top_ids.shape or top_scores.dtype not in (
+            torch.int32, torch.float32):
+        raise ValueError("top_scores must be int32 or float32 of top_ids' "
+                         "shape")
+    if top_scores.device != top_ids.device:
+        raise ValueError("top_ids and top_scores must share a device")
+    n_cols = top_ids.shape[0] if n_cols is None else int(n_cols)
+    if not 1 <= n_cols < 2 ** 31 or top_ids.shape[0] >= 2 ** 31:
+        raise ValueError("row and column counts must be below 2^31 and "
+                         "n_cols >= 1")
+    if top_ids.numel():
+        mn, mx = int(top_ids.min()), int(top_ids.max())
+        if mn < -1 or mx >= n_cols:
+            raise ValueError(f"top_ids out of range: [{mn}, {mx}] vs "
+                             f"[-1, {n_cols})")
+        ok = top_scores >= 0
+        if top_scores.dtype == torch.float32:
+            ok &= torch.isfinite(top_scores)
+        if not bool(ok.all()):
+            raise ValueError("top_scores must be >= 0 and finite")
+
+
+def _ind_check(top_ids, top_scores, q_indptr, q_items, K, n_cols,
+               ban_indptr, ban_indices, allow_indptr, allow_indices,
+               item_cats, query_cats, exclude_query, check_table):
+    """Everything indicator_topk validates, before any launch. Returns
+    (K, n_cols, lens int64 [B])."""
+    from predictionio_amd.ops.topk import _check_cats
+    K = int(K)
+    if not 1 <= K <= IND_K_MAX:
+        raise ValueError(f"K must be in [1, {IND_K_MAX}], got {K}")
+    if (top_ids.dim() != 2 or top_ids.dtype != torch.int32
+            or top_scores.shape != top_ids.shape
+            or top_scores.dtype not in (torch.int32, torch.float32)
+            or top_scores.device != top_ids.device):
+        raise ValueError("top_ids must be int32 [Nr, n] and top_scores int32"
+                         " or float32 of the same shape and device")
+    nr = top_ids.shape[0]
+    n_cols = nr if n_cols is None else int(n_cols)
+    if not 1 <= n_cols < 2 ** 31 or nr >= 2 ** 31:
+        raise ValueError("row and column counts must be below 2^31 and "
+                         "n_cols >= 1")
+    if exclude_query and n_cols != nr:
+        raise ValueError("exclude_query needs n_cols == the table's row "
+                         "count")
+    if q_indptr.dim() != 1 or q_indptr.numel() < 1:
+        raise ValueError("query CSR: indptr must be 1-D and not empty")
+    B = q_indptr.numel() - 1
+    _check_lists(q_indptr, q_items, B, nr, "query CSR")
+    lists = [q_indptr, q_items]
+    for ip, ix, name in ((ban_indptr, ban_indices, "ban list"),
+                         (allow_indptr, allow_indices, "allow list")):
+        if (ip is None) != (ix is None):
+            raise ValueError(f"{name}: indptr and indices must be given "
+                             "together")
+        if ip is not None:
+            _check_lists(ip, ix, B, n_cols, name)
+            lists += [ip, ix]
+    _check_cats(item_cats, query_cats, B, n_cols)
+    if item_cats is not None:
+        lists += [item_cats, query_cats]
+    if any(t.device != top_ids.device for t in lists):
+        raise ValueError("all tensors must be on the table's device")
+    if check_table:
+        check_indicator_table(top_ids, top_scores, n_cols)
+    lens = q_indptr[1:] - q_indptr[:-1]
+    if top_scores.dtype == torch.int32 and B and top_scores.numel():
+        if int(lens.max()) * int(top_scores.max()) >= 2 ** 31:
+            raise ValueError("count sums may reach 2^31: max query length x"
+                             " max count must stay below it")
+    return K, n_cols, lens
+
+
+def _ind_torch(top_ids, top_scores, q_indptr, q_items, queries, lens, K,
+               n_cols, ban, allow, item_cats, query_cats, exclude_query,
+               out_ids, out_sc, chunk: int = IND_REF_CHUNK):
+    """The definition in plain torch for the listed queries (int64 ids),
+    written into their rows of out_ids / out_sc. Entries are sorted by
+    (query, j, score bits); the canonical sum is then formed segment by
+    segment, position r of every segment added in step r. Chunked over
+    queries so that at most `chunk` table entries (or one query) are in
+    flight."""
+    import numpy as np
+    dev = top_ids.device
+    n = top_ids.shape[1]
+    is_float = top_scores.dtype == torch.float32
+    B = lens.numel()
+    if queries.numel() == 0 or n == 0:
+        return
+
+    def list_keys(indptr, indices):
+        qid = torch.repeat_interleave(torch.arange(B, device=dev),
+                                      indptr[1:] - indptr[:-1])
+        return qid * n_cols + indices.long()
+
+    own_keys = list_keys(q_indptr, q_items) if exclude_query else None
+    ban_keys = list_keys(*ban) if ban is not None else None
+    allow_keys = list_keys(*allow) if allow is not None else None
+
+    cum = np.cumsum((lens[queries] * n).cpu().numpy())
+    i = 0
+    while i < len(cum):
+        base = int(cum[i - 1]) if i else 0
+        e = max(int(np.searchsorted(cum, base + chunk, side="right")), i + 1)
+        qs = queries[i:e]
+        i = e
+        m = lens[qs]
+        total = int(m.sum())
+        if total == 0:
+            continue
+        rep = torch.repeat_interleave(torch.arange(qs.numel(), device=dev), m,
+                                      output_size=total)
+        off = torch.arange(total, device=dev) - (m.cumsum(0) - m)[rep]
+        rows = q_items[q_indptr[qs][rep] + off].long()
+        j = top_ids[rows].long().reshape(-1)
+        v = top_scores[rows].reshape(-1)
+        b = qs[rep].repeat_interleave(n)
+        keep = j >= 0
+        j, v, b = j[keep], v[keep], b[keep]
+        if j.numel() == 0:
+            continue
+        if is_float:
+            v = v + 0.0                           # -0.0 -> +0.0
+        bits = v.view(torch.int32).long()         # >= 0: value order
+        o = torch.argsort((j << 32) | bits)
+        o = o[torch.argsort(b[o], stable=True)]
+        j, v, b = j[o], v[o], b[o]
+        head = torch.ones(j.numel(), dtype=torch.bool, device=dev)
+        head[1:] = (b[1:] != b[:-1]) | (j[1:] != j[:-1])
+        start = head.nonzero().reshape(-1)
+        length = torch.diff(start, append=torch.tensor([j.numel()],
+                                                       device=dev))
+        acc = v[start].clone()
+        for r in range(1, int(length.max())):
+            sel = length > r
+            acc[sel] = acc[sel] + v[start[sel] + r]
+        sb, sj = b[start], j[start]
+        ok = torch.ones_like(sj, dtype=torch.bool)
+        key = sb * n_cols + sj
+        if own_keys is not None:
+            ok &= ~torch.isin(key, own_keys)
+        if ban_keys is not None:
+            ok &= ~torch.isin(key, ban_keys)
+        if allow_keys is not None:
+            ok &= torch.isin(key, allow_keys)
+        if item_cats is not None:
+            ok &= ((item_cats[sj] & query_cats[sb]) != 0).any(dim=1)
+        sb, sj, acc = sb[ok], sj[ok], acc[ok]
+        if sb.numel() == 0:
+            continue
+        o = torch.argsort((acc.view(torch.int32).long() << 32)
+                          | (0xFFFFFFFF - sj), descending=True)
+        o = o[torch.argsort(sb[o], stable=True)]
+        sb, sj, acc = sb[o], sj[o], acc[o]
+        first = torch.ones(sb.numel(), dtype=torch.bool, device=dev)
+        first[1:] = sb[1:] != sb[:-1]
+        pos = torch.arange(sb.numel(), device=dev)
+        rank = pos - torch.cummax(torch.where(first, pos, 0), 0).values
+        keep = rank < K
+        out_ids[sb[keep], rank[keep]] = sj[keep].to(torch.int32)
+        out_sc[sb[keep], rank[keep]] = acc[keep]
+
+
+def _ind_out(B: int, K: int, top_scores):
+    dev = top_scores.device
+    return (torch.full((B, K), -1, dtype=torch.int32, device=dev),
+            torch.zeros((B, K), dtype=top_scores.dtype, device=dev))
+
+
+def _opt_pair(indptr, indices):
+    return None if indptr is None else (indptr.contiguous(),
+                                        indices.contiguous())
+
+
+def indicator_topk_ref(top_ids, top_scores, q_indptr, q_items, K, *,
+                       n_cols=None, ban_indptr=None, ban_indices=None,
+                       allow_indptr=None, allow_indices=None, item_cats=None,
+                       query_cats=None, exclude_query=True, check_table=True,
+                       chunk: int = IND_REF_CHUNK):
+    """indicator_topk in plain torch on the inputs' device: the CPU path,
+    the route of queries above the kernel's cap, and what the GPU tests
+    compare against. Memory is O(chunk) table entries."""
+    K, n_cols, lens = _ind_check(
+        top_ids, top_scores, q_indptr, q_items, K, n_cols, ban_indptr,
+        ban_indices, allow_indptr, allow_indices, item_cats, query_cats,
+        exclude_query, check_table)
+    out_ids, out_sc = _ind_out(lens.numel(), K, top_scores)
+    _ind_torch(top_ids, top_scores, q_indptr, q_items,
+               torch.arange(lens.numel(), device=top_ids.device), lens, K,
+               n_cols, _opt_pair(ban_indptr, ban_indices),
+               _opt_pair(allow_indptr, allow_indices), item_cats, query_cats,
+               exclude_query, out_ids, out_sc, chunk)
+    return out_ids, out_sc
+
+
+def indicator_topk(top_ids, top_scores, q_indptr, q_items, K, *,
+                   n_cols=None, ban_indptr=None, ban_indices=None,
+                   allow_indptr=None, allow_indices=None, item_cats=None,
+                   query_cats=None, exclude_query=True, check_table=True):
+    """Sum the indicator rows of every query's items, filter and rank:
+    (ids int32 [B, K], scores [B, K] of top_scores.dtype), score
+    descending then id ascending, padded with -1 / 0.
+
+    top_ids int32 [Nr, n] (-1 padded) and top_scores int32 or float32
+    [Nr, n] (>= 0, finite) are what cooccurrence_topn /
+    cross_occurrence_topn return; n_cols (default Nr) is the id space of
+    top_ids' entries. (q_indptr int64 [B + 1], q_items int32) lists the
+    table rows of each query, strictly ascending. A candidate must pass
+    every filter given: not a row of the query itself (exclude_query;
+    needs n_cols == Nr), not in the query's ban list, in its allow list
+    (both CSRs like the query's, ids in [0, n_cols)), and the category
+    word test of topk_score (item_cats [n_cols, W], query_cats [B, W]).
+    Every argument is validated before any launch; check_table=False
+    skips the scan of the table for a caller that ran
+    check_indicator_table once.
+
+    GPU tensors go to csrc/indicator_topk.hip: queries of at most
+    IND_WAVE_MAX table entries (rows x n) to its one-wave instantiation,
+    of at most IND_WG_MAX to the 256-thread one, each a persistent launch
+    over its queries sorted by entry count; larger queries, and CPU
+    tensors, go through indicator_topk_ref. The route depends on the
+    query's own entry count alone and both routes form the same canonical
+    sum, so results do not depend on the batch."""
+    K, n_cols, lens = _ind_check(
+        top_ids, top_scores, q_indptr, q_items, K, n_cols, ban_indptr,
+        ban_indices, allow_indptr, allow_indices, item_cats, query_cats,
+        exclude_query, check_table)
+    B = lens.numel()
+    n = top_ids.shape[1]
+    dev = top_ids.device
+    out_ids, out_sc = _ind_out(B, K, top_scores)
+    ban = _opt_pair(ban_indptr, ban_indices)
+    allow = _opt_pair(allow_indptr, allow_indices)
+    top_ids, top_scores = top_ids.contiguous(), top_scores.contiguous()
+    q_indptr, q_items = q_indptr.contiguous(), q_items.contiguous()
+    if not top_ids.is_cuda:
+        _ind_torch(top_ids, top_scores, q_indptr, q_items,
+                   torch.arange(B, device=dev), lens, K, n_cols, ban, allow,
+                   item_cats, query_cats, exclude_query, out_ids, out_sc)
+        return out_ids, out_sc
+    if B == 0 or n == 0:
+        return out_ids, out_sc
+    from predictionio_amd.ops import hip_ext
+    ext = hip_ext()
+    E = lens * n
+    order = torch.argsort(E, descending=True, stable=True)
+    n_big, n_wg, n_live, m_wg, m_wave = torch.stack([
+        (E > IND_WG_MAX).sum(), (E > IND_WAVE_MAX).sum(), (E > 0).sum(),
+        torch.where(E <= IND_WG_MAX, lens, 0).max(),
+        torch.where(E <= IND_WAVE_MAX, lens, 0).max()]).tolist()
+    for work, threads, max_items in (
+            (order[n_big:n_wg], 256, m_wg), (order[n_wg:n_live], 64, m_wave)):
+        if work.numel():
+            ext.indicator_topk(
+                top_ids, top_scores, q_indptr, q_items,
+                work.to(torch.int32).contiguous(), max_items, threads, K,
+                n_cols, ban[0] if ban else None, ban[1] if ban else None,
+                allow[0] if allow else None, allow[1] if allow else None,
+                item_cats, query_cats, bool(exclude_query), out_ids, out_sc)
+    if n_big:
+        _ind_torch(top_ids, top_scores, q_indptr, q_items, order[:n_big],
+                   lens, K, n_cols, ban, allow, item_cats, query_cats,
+                   exclude_query, out_ids, out_sc)
+    return out_ids, out_sc

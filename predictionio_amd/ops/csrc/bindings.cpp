@@ -67,6 +67,17 @@ extern "C" void launch_topk_cand(
     int cw, int f, int K, int threads, float* out_val, int* out_idx,
     float* scores, int grid, hipStream_t stream);
 
+extern "C" int indicator_topk_cap(int threads);
+
+extern "C" void launch_indicator_topk(
+    const int* top_ids, const void* top_sc, int n, const long long* q_indptr,
+    const int* q_items, const int* work, int n_work, int max_items,
+    const long long* ban_indptr, const int* ban_indices,
+    const long long* allow_indptr, const int* allow_indices,
+    const int* item_cats, const int* query_cats, int cw, int is_float,
+    int exclude_own, int K, int threads, int n_cu, int* out_ids, void* out_sc,
+    hipStream_t stream);
+
 namespace {
 
 void check_cuda_f32(const torch::Tensor& t, const char* name) {
@@ -665,6 +676,108 @@ std::tuple<torch::Tensor, torch::Tensor> topk_cand(
   return {out_val, out_idx};
 }
 
+// One tier of indicator top-K (see indicator_topk.hip): the queries
+// listed in `work` (sorted by entry count descending; max_items = the row
+// count of work[0]) sum the rows of the indicator table that their CSR
+// segment names, filter and rank, and write their rows of out_ids /
+// out_scores [B, K] in place; rows not listed are left alone. threads 64
+// takes queries of at most indicator_topk_cap(64) entries (rows x n),
+// threads 256 of at most indicator_topk_cap(256). top_scores / out_scores
+// are int32 (counts) or fp32. The ban and allow CSRs are optional, each
+// given whole or not at all; exclude_query drops a query's own rows and
+// needs n_cols == Nr. All ids are trusted: ops/cooccurrence.py
+// range-checks the table, the query CSR and the lists first.
+void indicator_topk(torch::Tensor top_ids, torch::Tensor top_scores,
+                    torch::Tensor q_indptr, torch::Tensor q_items,
+                    torch::Tensor work, int64_t max_items, int64_t threads,
+                    int64_t K, int64_t n_cols,
+                    c10::optional<torch::Tensor> ban_indptr,
+                    c10::optional<torch::Tensor> ban_indices,
+                    c10::optional<torch::Tensor> allow_indptr,
+                    c10::optional<torch::Tensor> allow_indices,
+                    c10::optional<torch::Tensor> item_cats,
+                    c10::optional<torch::Tensor> query_cats,
+                    bool exclude_query, torch::Tensor out_ids,
+                    torch::Tensor out_scores) {
+  const auto dev = top_ids.device();
+  auto check = [&dev](const torch::Tensor& t, torch::ScalarType st,
+                      int64_t dim, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st &&
+                    t.dim() == dim && t.device() == dev,
+                name, " must be a contiguous ", dim, "-D ", c10::toString(st),
+                " tensor on the table's GPU");
+  };
+  const auto st = top_scores.scalar_type();
+  TORCH_CHECK(st == torch::kInt32 || st == torch::kFloat32,
+              "top_scores must be int32 or float32");
+  check(top_ids, torch::kInt32, 2, "top_ids");
+  check(top_scores, st, 2, "top_scores");
+  check(q_indptr, torch::kInt64, 1, "q_indptr");
+  check(q_items, torch::kInt32, 1, "q_items");
+  check(work, torch::kInt32, 1, "work");
+  check(out_ids, torch::kInt32, 2, "out_ids");
+  check(out_scores, st, 2, "out_scores");
+  TORCH_CHECK(top_scores.sizes() == top_ids.sizes(),
+              "top_ids and top_scores must have one shape");
+  const int64_t Nr = top_ids.size(0);
+  const int64_t n = top_ids.size(1);
+  const int64_t B = q_indptr.size(0) - 1;
+  TORCH_CHECK(B >= 0, "q_indptr must not be empty");
+  TORCH_CHECK(Nr < (1LL << 31) && n_cols >= 1 && n_cols < (1LL << 31) &&
+                  B < (1LL << 31) && n < (1LL << 31),
+              "row, column and query counts must be below 2^31");
+  TORCH_CHECK(K >= 1 && K <= 1024, "K must be in [1, 1024], got ", K);
+  TORCH_CHECK(out_ids.size(0) == B && out_ids.size(1) == K &&
+                  out_scores.size(0) == B && out_scores.size(1) == K,
+              "out_ids and out_scores must be [B, K]");
+  TORCH_CHECK(threads == 64 || threads == 256, "threads must be 64 or 256");
+  TORCH_CHECK(!exclude_query || n_cols == Nr,
+              "exclude_query needs n_cols == the table's row count");
+  TORCH_CHECK(max_items >= 0 &&
+                  max_items * n <= indicator_topk_cap((int)threads),
+              "a query of ", max_items, " rows x ", n,
+              " entries exceeds this instantiation's cap");
+  auto opt_csr = [&](const c10::optional<torch::Tensor>& ip,
+                     const c10::optional<torch::Tensor>& ix, const char* name,
+                     const long long*& ip_ptr, const int*& ix_ptr) {
+    TORCH_CHECK(ip.has_value() == ix.has_value(), name,
+                ": indptr and indices must be given together");
+    if (!ip.has_value()) return;
+    check(*ip, torch::kInt64, 1, name);
+    check(*ix, torch::kInt32, 1, name);
+    TORCH_CHECK(ip->size(0) == B + 1, name, ": indptr must be B + 1");
+    ip_ptr = reinterpret_cast<const long long*>(ip->data_ptr<int64_t>());
+    ix_ptr = ix->data_ptr<int>();
+  };
+  const long long* ban_p = nullptr;
+  const long long* allow_p = nullptr;
+  const int* ban_x = nullptr;
+  const int* allow_x = nullptr;
+  opt_csr(ban_indptr, ban_indices, "ban list", ban_p, ban_x);
+  opt_csr(allow_indptr, allow_indices, "allow list", allow_p, allow_x);
+  const int cw = check_cats(item_cats, query_cats, B, n_cols, false);
+  TORCH_CHECK(cw == 0 || (item_cats->device() == dev &&
+                          query_cats->device() == dev),
+              "category words must be on the table's GPU");
+  const int64_t n_work = work.size(0);
+  if (n_work == 0 || max_items == 0 || n == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const int n_cu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_indicator_topk(
+      top_ids.data_ptr<int>(), top_scores.data_ptr(), (int)n,
+      reinterpret_cast<const long long*>(q_indptr.data_ptr<int64_t>()),
+      q_items.data_ptr<int>(), work.data_ptr<int>(), (int)n_work,
+      (int)max_items, ban_p, ban_x, allow_p, allow_x,
+      cw ? item_cats->data_ptr<int>() : nullptr,
+      cw ? query_cats->data_ptr<int>() : nullptr, cw,
+      st == torch::kFloat32 ? 1 : 0, exclude_query ? 1 : 0, (int)K,
+      (int)threads, n_cu, out_ids.data_ptr<int>(), out_scores.data_ptr(),
+      stream);
+  C10_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -719,4 +832,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scores") = py::none());
   m.def("cooc_dense_lds_max", &cooc_dense_lds_max,
         "Largest item count of the LDS dense tier");
+  m.def("indicator_topk", &indicator_topk,
+        "Indicator top-K of the listed queries, one tier",
+        py::arg("top_ids"), py::arg("top_scores"), py::arg("q_indptr"),
+        py::arg("q_items"), py::arg("work"), py::arg("max_items"),
+        py::arg("threads"), py::arg("K"), py::arg("n_cols"),
+        py::arg("ban_indptr"), py::arg("ban_indices"),
+        py::arg("allow_indptr"), py::arg("allow_indices"),
+        py::arg("item_cats"), py::arg("query_cats"),
+        py::arg("exclude_query"), py::arg("out_ids"), py::arg("out_scores"));
+  m.def("indicator_topk_cap", &indicator_topk_cap,
+        "Largest entry count per query of the 64- / 256-thread kernel",
+        py::arg("threads"));
 }

@@ -362,6 +362,43 @@ class CooccurrenceModel:
         self.items = items
         self.item_inv = item_map.inverse_array()
 
+    def device_table(self):
+        """(top_ids, top_scores) as tensors on the serving device, built
+        from the host copies and checked against indicator_topk's table
+        contract once, on first use; None for a model without a table."""
+        if self.top_ids is None:
+            return None
+        if getattr(self, "_device_table", None) is None:
+            from predictionio_amd.ops.cooccurrence import (
+                check_indicator_table,
+            )
+            dev = getattr(self, "_device", None) or (
+                torch.device("cuda") if torch.cuda.is_available()
+                else torch.device("cpu"))
+            ids = torch.from_numpy(self.top_ids).to(dev).contiguous()
+            sc = torch.from_numpy(self.top_cnt).to(dev).contiguous()
+            check_indicator_table(ids, sc, len(self.item_map))
+            self._device_table = (ids, sc)
+        return self._device_table
+
+    def to(self, device) -> "CooccurrenceModel":
+        """Serve from `device`: the table and the category words are
+        rebuilt there on their next use."""
+        self._device = torch.device(device)
+        self._device_table = None
+        self._cat_bits_built = False
+        return self
+
+    def cat_bits(self):
+        """CategoryBits words on the table's device, built on first use;
+        None when the catalog has more than 127 categories."""
+        if not getattr(self, "_cat_bits_built", False):
+            from predictionio_amd.templates.common import CategoryBits
+            self.category_bits = CategoryBits.build(
+                self.items, self.item_map, self.device_table()[0].device)
+            self._cat_bits_built = True
+        return self.category_bits
+
 
 class CooccurrenceAlgorithm(Algorithm):
     """Params: n (top co-occurrences kept per item)
@@ -420,8 +457,11 @@ class CooccurrenceAlgorithm(Algorithm):
             k = int((top_ids[it] >= 0).sum())
             top_n[it] = list(zip(top_ids[it, :k].tolist(),
                                  top_cnt[it, :k].tolist()))
-        return CooccurrenceModel(top_n, item_map, pd.items,
-                                 top_ids=top_ids, top_cnt=top_cnt)
+        model = CooccurrenceModel(top_n, item_map, pd.items,
+                                  top_ids=top_ids, top_cnt=top_cnt)
+        model.device_table()  # built and checked once, for batch_predict
+        model.cat_bits()
+        return model
 
     def predict(self, model: CooccurrenceModel, query) -> PredictedResult:
         q = query if isinstance(query, Query) else Query.from_json(query)
@@ -454,6 +494,77 @@ class CooccurrenceAlgorithm(Algorithm):
                         reverse=True)[:q.num]
         return PredictedResult([
             ItemScore(model.item_inv[i], float(c)) for c, i in ranked])
+
+    def batch_predict(self, model: CooccurrenceModel, queries):
+        """Device-batched predict: one indicator_topk call (two when some
+        queries carry a whiteList: they form a group of their own, so the
+        others are not restricted by an allow list). Per query the known
+        items become a row of the query CSR, blackList a row of the ban
+        CSR, whiteList a row of the allow CSR and `categories` a row of
+        category bit words; the query's own items are excluded by the op.
+        Unknown items are dropped, as in predict. Scores of an "llr"
+        model are the canonical fp32 sums of the op where predict adds in
+        double. One documented difference: on equal scores the order here
+        is item index ascending, in predict descending. Queries predict
+        treats specially (a repeated item, num outside [1, 1024]), models
+        without a table and catalogs with more than 127 categories go
+        through predict one by one."""
+        import numpy as np
+        from predictionio_amd.ops.cooccurrence import (
+            IND_K_MAX, indicator_topk,
+        )
+        from predictionio_amd.templates.common import ban_csr
+        qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
+              for i, q in queries]
+        table = model.device_table()
+        bits = model.cat_bits() if table is not None else None
+        if bits is None:
+            return [(i, self.predict(model, q)) for i, q in qs]
+        ids_t, sc_t = table
+        dev = ids_t.device
+        imap = model.item_map
+
+        def known(names):
+            return sorted({imap[x] for x in names if x in imap})
+
+        out: Dict[int, PredictedResult] = {}
+        groups = ([], [])  # (i, q, query item rows): plain, whiteList
+        for i, q in qs:
+            rows = known(q.items)
+            if (len(rows) != sum(x in imap for x in q.items)
+                    or not 1 <= q.num <= IND_K_MAX):
+                out[i] = self.predict(model, q)
+            elif rows:
+                groups[q.white_list is not None].append((i, q, rows))
+            else:
+                out[i] = PredictedResult([])
+        inv = np.asarray(model.item_inv, dtype=object)
+        for white, group in enumerate(groups):
+            if not group:
+                continue
+            q_indptr, q_items = ban_csr([g[2] for g in group], dev)
+            ban_indptr, ban_indices = ban_csr(
+                [known(g[1].black_list or []) for g in group], dev)
+            kw = {}
+            if white:
+                kw["allow_indptr"], kw["allow_indices"] = ban_csr(
+                    [known(g[1].white_list) for g in group], dev)
+            query_cats = torch.from_numpy(np.stack(
+                [bits.query_words(g[1].categories) for g in group])).to(dev)
+            ids, sc = indicator_topk(
+                ids_t, sc_t, q_indptr, q_items, max(g[1].num for g in group),
+                n_cols=len(imap), ban_indptr=ban_indptr,
+                ban_indices=ban_indices, item_cats=bits.item_words,
+                query_cats=query_cats, exclude_query=True, check_table=False,
+                **kw)
+            ids_np, sc_np = ids.cpu().numpy(), sc.cpu().numpy()
+            names = inv[np.clip(ids_np, 0, None)]
+            for r, (i, q, _) in enumerate(group):
+                out[i] = PredictedResult(
+                    [ItemScore(nm, float(s)) for nm, s, it in
+                     zip(names[r, :q.num], sc_np[r, :q.num],
+                         ids_np[r, :q.num]) if it >= 0])
+        return [(i, out[i]) for i, _ in qs]
 
 
 class Serving(BaseServing):
