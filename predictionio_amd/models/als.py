@@ -282,6 +282,53 @@ class ALSTrainer:
         return als_ops.combine_objective(A, B, reg, frob, int(nnz),
                                          p.lambda_, p.implicit)
 
+    def heldout(self, test_users: torch.Tensor, test_items: torch.Tensor,
+                test_values: Optional[torch.Tensor] = None,
+                ks=(10,)) -> dict:
+        """Ranking quality on held-out (user, item) pairs at the current
+        factors: the dict of ops.ranking.ranking_metrics (mpr, auc,
+        recall@K, mrr, ndcg@K, n_users, n_pairs). Every held-out item is
+        ranked against all items its user has no training rating for;
+        test_values, if given, weight the pairs in mpr (the rank-bar of
+        Hu, Koren and Volinsky). A pair that is also a training rating,
+        or one given twice, raises ValueError.
+
+        Single process only: the ranks need a user's row against all of
+        Y and this rank's slice of the users would give a partial mean."""
+        if pdist.get_world_size() > 1:
+            raise NotImplementedError(
+                "ALSTrainer.heldout is single-process: sharded held-out "
+                "evaluation is not implemented; evaluate gather_factors() "
+                "with ops.ranking.heldout_ranks on one device instead")
+        from predictionio_amd.ops import ranking
+        d = self.device
+        N = self.n_items
+        key, order = torch.sort(test_users.to(d).long() * N
+                                + test_items.to(d).long())
+        users, inv = torch.unique(key // N, return_inverse=True)
+        t_ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=d)
+        torch.cumsum(torch.bincount(inv, minlength=users.numel()), 0,
+                     out=t_ptr[1:])
+        t_idx = (key % N).to(torch.int32)
+        # the users' training rows, sorted and without repeats
+        indptr, indices, _ = self.user_csr
+        lens = indptr[users + 1] - indptr[users]
+        start = torch.cumsum(lens, 0) - lens
+        src = (torch.repeat_interleave(indptr[users] - start, lens)
+               + torch.arange(int(lens.sum()), device=d))
+        row = torch.repeat_interleave(torch.arange(users.numel(), device=d),
+                                      lens)
+        skey = torch.unique(row * N + indices[src].long())
+        s_ptr = torch.zeros(users.numel() + 1, dtype=torch.int64, device=d)
+        torch.cumsum(torch.bincount(skey // N, minlength=users.numel()), 0,
+                     out=s_ptr[1:])
+        s_idx = (skey % N).to(torch.int32)
+        gt, eq, n_cand = ranking.heldout_ranks(
+            self.X[users].contiguous(), self.Y, t_ptr, t_idx, s_ptr, s_idx)
+        w = None if test_values is None else test_values.to(d)[order]
+        return ranking.ranking_metrics(gt, eq, n_cand, t_ptr, ks=ks,
+                                       weights=w)
+
     def _record_loss(self, iteration: int) -> bool:
         """Evaluate the objective after `iteration`, append it to
         loss_history, log it; True when tol says to stop. The value is

@@ -18,7 +18,8 @@ CSRC = os.path.join(OPS_DIR, "csrc")
 SO_PATH = os.path.join(OPS_DIR, "_pio_hip.so")
 SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
            "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
-           "cooc_topn.hip", "topk_cand.hip", "indicator_topk.hip"]
+           "cooc_topn.hip", "topk_cand.hip", "indicator_topk.hip",
+           "rank_count.hip"]
 # compiled on their own with packed fp32 VALU ops off (the vectorizer may
 # otherwise pair independent fp32 chains), then linked with the rest.
 # cooc_topn.hip is here since its LLR score stage: today it holds no
@@ -28,7 +29,11 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
 # file includes only the HIP runtime, so it needs none of the torch -D's.
 # indicator_topk.hip: its fp32 segment sums are an ordered chain of adds
 # (the canonical sum) and must stay one.
-NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip", "indicator_topk.hip"]
+# rank_count.hip: its scores live on the matrix pipe and its epilogue is
+# compares and integer adds, so the flag changes nothing today; it keeps
+# fp32 VALU code added to it later from being packed unnoticed.
+NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip", "indicator_topk.hip",
+                  "rank_count.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

@@ -78,6 +78,20 @@ extern "C" void launch_indicator_topk(
     int exclude_own, int K, int threads, int n_cu, int* out_ids, void* out_sc,
     hipStream_t stream);
 
+extern "C" int rank_count_tmax();
+extern "C" int rank_count_group();
+extern "C" int rank_stream_lds_bytes(int f);
+
+extern "C" void launch_rank_list(
+    const float* X, const float* Y, const int* slot_user, const int* slot_tgt,
+    const long long* seen_indptr, const int* seen_indices, float* tscore,
+    int* corr, int n_slots, int f, hipStream_t stream);
+
+extern "C" void launch_rank_stream(
+    const float* X, const float* Y, long long N, const int* slot_user,
+    const float* tscore, int n_slots, int n_slices, int ties, int* partial,
+    int f, hipStream_t stream);
+
 namespace {
 
 void check_cuda_f32(const torch::Tensor& t, const char* name) {
@@ -778,6 +792,108 @@ void indicator_topk(torch::Tensor top_ids, torch::Tensor top_scores,
   C10_HIP_CHECK(hipGetLastError());
 }
 
+// Held-out rank counts (see rank_count.hip). The slot arrays come from
+// ops/ranking.py: slot_user [S] names the X row of each slot, slot_tgt
+// [S, TMAX] its target item ids (-1 = none), S a multiple of the slot
+// group. Ids are trusted: the wrapper validates the CSRs first.
+void check_rank_common(const torch::Tensor& X, const torch::Tensor& Y,
+                       const torch::Tensor& slot_user) {
+  check_cuda_f32(X, "X");
+  check_cuda_f32(Y, "Y");
+  TORCH_CHECK(X.dim() == 2 && Y.dim() == 2 && X.size(1) == Y.size(1) &&
+                  supported_rank(X.size(1)),
+              "X and Y must be 2-D with one rank in {16, 32, 64, 128}");
+  TORCH_CHECK(X.size(0) >= 1 && Y.size(0) >= 1 &&
+                  Y.size(0) < (1LL << 31) && X.size(0) < (1LL << 31),
+              "X and Y need between 1 and 2^31 - 1 rows");
+  TORCH_CHECK(slot_user.is_cuda() && slot_user.is_contiguous() &&
+                  slot_user.scalar_type() == torch::kInt32 &&
+                  slot_user.dim() == 1 &&
+                  slot_user.size(0) % rank_count_group() == 0 &&
+                  slot_user.size(0) < (1LL << 31),
+              "slot_user must be a contiguous 1-D int32 GPU tensor, its "
+              "length a multiple of ", rank_count_group());
+  TORCH_CHECK(Y.device() == X.device() && slot_user.device() == X.device(),
+              "all tensors must be on one GPU");
+}
+
+// Target scores and seen-list corrections: (tscore [S, TMAX] fp32,
+// corr [S, 2, TMAX] int32 = seen items scoring > / >= each target).
+std::vector<torch::Tensor> rank_list(
+    torch::Tensor X, torch::Tensor Y, torch::Tensor slot_user,
+    torch::Tensor slot_tgt, c10::optional<torch::Tensor> seen_indptr,
+    c10::optional<torch::Tensor> seen_indices) {
+  check_rank_common(X, Y, slot_user);
+  const int64_t S = slot_user.size(0);
+  const int T = rank_count_tmax();
+  TORCH_CHECK(slot_tgt.is_cuda() && slot_tgt.is_contiguous() &&
+                  slot_tgt.scalar_type() == torch::kInt32 &&
+                  slot_tgt.dim() == 2 && slot_tgt.size(0) == S &&
+                  slot_tgt.size(1) == T && slot_tgt.device() == X.device(),
+              "slot_tgt must be a contiguous [S, ", T, "] int32 GPU tensor");
+  TORCH_CHECK(seen_indptr.has_value() == seen_indices.has_value(),
+              "seen_indptr and seen_indices must be given together");
+  const long long* sp = nullptr;
+  const int* sx = nullptr;
+  if (seen_indptr.has_value()) {
+    TORCH_CHECK(seen_indptr->is_cuda() && seen_indptr->is_contiguous() &&
+                    seen_indptr->scalar_type() == torch::kInt64 &&
+                    seen_indptr->dim() == 1 &&
+                    seen_indptr->size(0) == X.size(0) + 1 &&
+                    seen_indptr->device() == X.device(),
+                "seen_indptr must be a contiguous int64 GPU tensor of "
+                "X's rows + 1");
+    TORCH_CHECK(seen_indices->is_cuda() && seen_indices->is_contiguous() &&
+                    seen_indices->scalar_type() == torch::kInt32 &&
+                    seen_indices->dim() == 1 &&
+                    seen_indices->device() == X.device(),
+                "seen_indices must be a contiguous 1-D int32 GPU tensor");
+    sp = reinterpret_cast<const long long*>(seen_indptr->data_ptr<int64_t>());
+    sx = seen_indices->data_ptr<int>();
+  }
+  auto tscore = torch::empty({S, T}, X.options());
+  auto corr = torch::empty({S, 2, T}, slot_user.options());
+  if (S == 0) return {tscore, corr};
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_rank_list(X.data_ptr<float>(), Y.data_ptr<float>(),
+                   slot_user.data_ptr<int>(), slot_tgt.data_ptr<int>(), sp, sx,
+                   tscore.data_ptr<float>(), corr.data_ptr<int>(), (int)S,
+                   (int)X.size(1), stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {tscore, corr};
+}
+
+// partial [n_slices, S, 2, TMAX] int32: per item slice, how many of its
+// items score > (row 0) and, with ties, >= (row 1) each target score.
+// Without ties row 1 is not written.
+torch::Tensor rank_stream(torch::Tensor X, torch::Tensor Y,
+                          torch::Tensor slot_user, torch::Tensor tscore,
+                          int64_t n_slices, bool ties) {
+  check_rank_common(X, Y, slot_user);
+  const int64_t S = slot_user.size(0);
+  const int T = rank_count_tmax();
+  check_cuda_f32(tscore, "tscore");
+  TORCH_CHECK(tscore.dim() == 2 && tscore.size(0) == S &&
+                  tscore.size(1) == T && tscore.device() == X.device(),
+              "tscore must be [S, ", T, "]");
+  TORCH_CHECK(n_slices >= 1 && n_slices <= 65535,
+              "n_slices must be in [1, 65535], got ", n_slices);
+  auto partial = torch::empty({n_slices, S, 2, T}, slot_user.options());
+  if (S == 0) return partial;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_rank_stream(X.data_ptr<float>(), Y.data_ptr<float>(),
+                     (long long)Y.size(0), slot_user.data_ptr<int>(),
+                     tscore.data_ptr<float>(), (int)S, (int)n_slices,
+                     ties ? 1 : 0, partial.data_ptr<int>(), (int)X.size(1),
+                     stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return partial;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -844,4 +960,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("indicator_topk_cap", &indicator_topk_cap,
         "Largest entry count per query of the 64- / 256-thread kernel",
         py::arg("threads"));
+  m.def("rank_list", &rank_list,
+        "Held-out ranks: target scores and seen-list corrections per slot",
+        py::arg("X"), py::arg("Y"), py::arg("slot_user"), py::arg("slot_tgt"),
+        py::arg("seen_indptr") = py::none(),
+        py::arg("seen_indices") = py::none());
+  m.def("rank_stream", &rank_stream,
+        "Held-out ranks: per-slice counts of items beating each target",
+        py::arg("X"), py::arg("Y"), py::arg("slot_user"), py::arg("tscore"),
+        py::arg("n_slices"), py::arg("ties") = true);
+  m.def("rank_count_tmax", &rank_count_tmax, "Targets per slot");
+  m.def("rank_count_group", &rank_count_group, "Slots per workgroup");
+  m.def("rank_stream_lds_bytes", &rank_stream_lds_bytes,
+        "Dynamic LDS of the stream kernel at rank f", py::arg("f"));
 }
