@@ -21,6 +21,18 @@ def pad_rank(f: int) -> int:
     raise ValueError(f"rank {f} > 128 not supported")
 
 
+ROW_LIMIT = 2 ** 31  # the kernels carry row counts and row ids as int
+
+
+def check_row_count(**counts: int) -> None:
+    """ValueError when a row count reaches 2^31. Callers run it on the
+    shapes alone, before any copy, padding or launch."""
+    for name, n in counts.items():
+        if n >= ROW_LIMIT:
+            raise ValueError(
+                f"{name} = {n} rows: row counts must be below 2^31")
+
+
 def gramian(Y: torch.Tensor) -> torch.Tensor:
     """YtY (f x f) — a plain library GEMM (hipBLASLt on device)."""
     return Y.t() @ Y
@@ -30,6 +42,7 @@ def row_transform(A: torch.Tensor, W: torch.Tensor,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A[N, f] @ W[f, f] on the GPU's hand-written row-transform kernel
     (fp32 in, fp32 accumulate). `out`, if given, is written in place."""
+    check_row_count(A=A.shape[0])
     from predictionio_amd.ops import hip_ext
     return hip_ext().als_row_transform(A.contiguous(), W.contiguous(), out)
 
@@ -88,6 +101,7 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
     whole; indptr offsets are absolute). out: optional [rows, f] target
     written in place (enables chunked solves into one padded buffer).
     """
+    check_row_count(indptr=indptr.shape[0] - 1, Y=Y.shape[0])
     if implicit:
         wr_scale = False  # Hu-Koren regularizes with plain lambda*I
         if YtY is None:
@@ -261,6 +275,7 @@ def als_residual_sums(indptr: torch.Tensor, indices: torch.Tensor,
     where they lie: any rank 1 <= f <= 128, unpadded fp32 factors, fp32
     fma-chain dots, fp64 from there on, bit-reproducible. pred, if given
     ([nnz] fp32), receives s per rating. On CPU: als_residual_sums_ref."""
+    check_row_count(indptr=indptr.shape[0] - 1, X=X.shape[0], Y=Y.shape[0])
     if not X.is_cuda:
         return als_residual_sums_ref(indptr, indices, values, X, Y, alpha,
                                      implicit, pred)

@@ -109,6 +109,14 @@ __global__ __launch_bounds__(256) void als_xform_kernel(
           acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(
               w[ct][4 * q + t], a[q][t], acc[ct], 0, 0, 0);
 
+    // in place (out == in), the CG waves that share a row tile each read
+    // whole rows and overwrite their own columns: none may store before
+    // all of them hold the tile. They run the same trips (one tile per
+    // workgroup pass), so the barrier is uniform.
+    if constexpr (CG > 1) {
+      static_assert(TPW == 1, "waves sharing a tile must be the workgroup");
+      if (in == out) __syncthreads();
+    }
     const long long row = tile * 32 + r;
     if (row < n_rows) {
       float* orow = out + row * F + cbase + 4 * h;

@@ -476,6 +476,9 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
 // idx, so the upper bound is checked here (one small reduction).
 torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
                            torch::Tensor idx) {
+  // idx is int32: checked first, before anything looks at the data
+  TORCH_CHECK_VALUE(Y.dim() == 2 && Y.size(0) < (1LL << 31),
+                    "the item count N must be below 2^31");
   check_cuda_f32(Xq, "Xq");
   check_cuda_f32(Y, "Y");
   TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2 && idx.dim() == 2,

@@ -32,6 +32,16 @@ def _check_csr(indptr: torch.Tensor, indices: torch.Tensor, B: int,
         raise ValueError(f"{name}_indices must be a 1-D int32 tensor")
 
 
+def _not_finite(t: torch.Tensor) -> torch.Tensor:
+    """Scalar bool tensor: t holds a NaN or an infinity. One min/max
+    reduction (both propagate NaN) and no temporary: isfinite(t).all()
+    allocated 1.75 times the size of a multi-GB factor matrix."""
+    if t.numel() == 0:
+        return torch.zeros((), dtype=torch.bool, device=t.device)
+    mn, mx = torch.aminmax(t)
+    return ~(torch.isfinite(mn) & torch.isfinite(mx))
+
+
 def _validate(X, Y, test_indptr, test_indices, seen_indptr, seen_indices):
     """The contract of heldout_ranks, checked on the tensors' device with
     one transfer to the host. Every id the kernels gather by is checked
@@ -63,8 +73,7 @@ def _validate(X, Y, test_indptr, test_indices, seen_indptr, seen_indices):
         flags.append(cond.reshape(()))
         names.append(msg)
 
-    flag(~torch.isfinite(X).all() | ~torch.isfinite(Y).all(),
-         "X and Y must be finite")
+    flag(_not_finite(X) | _not_finite(Y), "X and Y must be finite")
     keys = []
     for name, ip, ci in lists:
         nnz = ci.numel()

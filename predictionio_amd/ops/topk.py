@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch.utils.weak import WeakTensorKeyDictionary
 
-from predictionio_amd.ops.als import pad_rank
+from predictionio_amd.ops.als import check_row_count, pad_rank
 
 log = logging.getLogger(__name__)
 
@@ -101,6 +101,7 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
+    check_row_count(Xq=B, Y=N)
     _check_cats(item_cats, query_cats, B, N)
     if (cand_indptr is None) != (cand_indices is None):
         raise ValueError(
@@ -391,6 +392,7 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     from predictionio_amd.ops import hip_ext
     B, f = Xq.shape
     N = Y.shape[0]
+    check_row_count(Xq=B, Y=N)
     pf = _mfma_rank(f)
     if pf is None or B == 0:
         return None
@@ -410,8 +412,7 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         item_cats=item_cats, query_cats=query_cats,
         interleave=True, gth=False)
     short_idx, _, flagged = _union_merge(vals, idxs, L, S, M)
-    exact = ext.topk_rescore(Xq.contiguous(), Y.contiguous(),
-                             short_idx.to(torch.int32))
+    exact = topk_rescore(Xq, Y, short_idx.to(torch.int32))
     mv, p2 = torch.topk(exact, min(K, exact.shape[1]), dim=1)
     midx = torch.gather(short_idx, 1, p2)
     midx[mv == float("-inf")] = -1
@@ -446,6 +447,16 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     return mv, midx
 
 
+def topk_rescore(Xq: torch.Tensor, Y: torch.Tensor,
+                 idx: torch.Tensor) -> torch.Tensor:
+    """out[b, c] = Xq[b] . Y[idx[b, c]] in fp32 on the GPU
+    (csrc/topk_rescore.hip), -inf where idx < 0. idx [B, C] int32; Xq and
+    Y are read where they lie."""
+    check_row_count(Xq=Xq.shape[0], Y=Y.shape[0])
+    from predictionio_amd.ops import hip_ext
+    return hip_ext().topk_rescore(Xq.contiguous(), Y.contiguous(), idx)
+
+
 def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                      item_mask, ban_indptr, ban_indices,
                      n_slices: Optional[int],
@@ -468,6 +479,7 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     from predictionio_amd.ops import hip_ext
     B, f = Xq.shape
     N = Y.shape[0]
+    check_row_count(Xq=B, Y=N)
     pf = _mfma_rank(f)
     Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
     # the per-slice list length IS the shortlist depth: with a list of K
@@ -620,6 +632,7 @@ def _topk_score_cands(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     from predictionio_amd.ops import hip_ext
     B, f = Xq.shape
     N = Y.shape[0]
+    check_row_count(Xq=B, Y=N)
     if K < 1:
         raise ValueError("K must be >= 1")
     if seg_len < 1 or wave_max < 0:
@@ -692,6 +705,7 @@ def topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
     score descending then id ascending. O(nnz * f) memory."""
     B, N = Xq.shape[0], Y.shape[0]
     K = int(K)
+    check_row_count(Xq=B, Y=N)
     if K < 1:
         raise ValueError("K must be >= 1")
     _check_cats(item_cats, query_cats, B, N)
@@ -719,6 +733,7 @@ def topk_score_ref(Xq, Y, K, item_mask=None, ban_indptr=None,
                    cand_indptr=None, cand_indices=None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch reference (CPU path + GPU numerics baseline)."""
+    check_row_count(Xq=Xq.shape[0], Y=Y.shape[0])
     if (cand_indptr is None) != (cand_indices is None):
         raise ValueError(
             "cand_indptr and cand_indices must be given together")

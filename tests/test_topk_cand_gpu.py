@@ -170,19 +170,22 @@ def test_views_and_alignment():
 
 
 def test_row_offsets_past_4gib():
-    """Rows beyond the 2^32 byte offset of Y: 64-bit row addressing."""
+    """Rows beyond the 2^31 and 2^32 byte offsets of Y, with the rows 2
+    and 4 GiB above row 5 planted too: 64-bit row addressing. (Both
+    tiers and scores mode: test_large_offsets_gpu.py.)"""
     n, f = 2 ** 24 + 64, 64
     Y = torch.zeros((n, f), device="cuda")
-    rows = [5, 2 ** 24 - 1, 2 ** 24, 2 ** 24 + 7, n - 1]
+    rows = [5, 2 ** 23 - 1, 2 ** 23, 2 ** 23 + 5, 2 ** 24 - 1, 2 ** 24,
+            2 ** 24 + 5, 2 ** 24 + 7, n - 1]
     for r, j in enumerate(rows):
         Y[j, r] = float(r + 1)
         Y[j, 63] = 1.0
     Xq = torch.ones((1, f), device="cuda")
     ip, ci = _csr([rows])
-    v, i = topk_ops.topk_score(Xq, Y, 3, cand_indptr=ip.cuda(),
+    v, i = topk_ops.topk_score(Xq, Y, 9, cand_indptr=ip.cuda(),
                                cand_indices=ci.cuda())
-    assert i[0].tolist() == [n - 1, 2 ** 24 + 7, 2 ** 24]
-    assert v[0].tolist() == [6.0, 5.0, 4.0]
+    assert i[0].tolist() == rows[::-1]
+    assert v[0].tolist() == [float(r + 2) for r in range(8, -1, -1)]
 
 
 @pytest.mark.parametrize("ip,ci", [
