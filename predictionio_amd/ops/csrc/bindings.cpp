@@ -28,7 +28,7 @@ extern "C" void launch_topk_score(
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof,
     const int* item_cats, const int* query_cats, int cw,
-    hipStream_t stream);
+    const float* item_weights, hipStream_t stream);
 
 extern "C" void launch_topk_mfma(
     const unsigned short* Xq, const unsigned short* Y,
@@ -37,11 +37,11 @@ extern "C" void launch_topk_mfma(
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof, unsigned* th_g,
     const int* item_cats, const int* query_cats, int cw, int interleave,
-    hipStream_t stream);
+    const float* item_weights, hipStream_t stream);
 
 extern "C" void launch_topk_rescore(
-    const float* Xq, const float* Y, const int* idx, float* out,
-    long long B, int C, int f, hipStream_t stream);
+    const float* Xq, const float* Y, const int* idx, const float* w,
+    float* out, long long B, int C, int f, hipStream_t stream);
 
 extern "C" int als_loss_grid(long long n_rows, int n_cu);
 
@@ -64,8 +64,9 @@ extern "C" void launch_topk_cand(
     const float* Xq, const float* Y, const int* cand, const long long* segs,
     int n_segs, const uint8_t* item_mask, const long long* ban_indptr,
     const int* ban_indices, const int* item_cats, const int* query_cats,
-    int cw, int f, int K, int threads, float* out_val, int* out_idx,
-    float* scores, int grid, hipStream_t stream);
+    const float* item_weights, int cw, int f, int K, int threads,
+    float* out_val, int* out_idx, float* scores, int grid,
+    hipStream_t stream);
 
 extern "C" int indicator_topk_cap(int threads);
 
@@ -184,6 +185,24 @@ TopkArgs check_topk_args(const c10::optional<torch::Tensor>& item_mask,
         prof->data_ptr<uint64_t>());
   }
   return a;
+}
+
+// Per-item score weights of the top-K entries: a contiguous fp32 [N]
+// tensor on the factors' device, or not given (nullptr). A mismatch
+// raises ValueError; there is no fallback. With the phase probe the
+// kernels have no weighted instantiation.
+const float* check_item_weights(const c10::optional<torch::Tensor>& w,
+                                const torch::Tensor& Y, bool prof) {
+  if (!w.has_value()) return nullptr;
+  TORCH_CHECK_VALUE(!prof, "prof cannot be combined with item_weights");
+  TORCH_CHECK_VALUE(w->scalar_type() == torch::kFloat32,
+                    "item_weights must be fp32");
+  TORCH_CHECK_VALUE(w->dim() == 1 && w->size(0) == Y.size(0),
+                    "item_weights must have shape [N]");
+  TORCH_CHECK_VALUE(w->is_contiguous(), "item_weights must be contiguous");
+  TORCH_CHECK_VALUE(w->is_cuda() && w->device() == Y.device(),
+                    "item_weights must be on the device of Y");
+  return w->data_ptr<float>();
 }
 
 // Solve one ALS half-iteration: for every CSR row r,
@@ -371,9 +390,11 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
     c10::optional<torch::Tensor> ban_indices, int64_t item_base,
     c10::optional<torch::Tensor> prof,
     c10::optional<torch::Tensor> item_cats,
-    c10::optional<torch::Tensor> query_cats) {
+    c10::optional<torch::Tensor> query_cats,
+    c10::optional<torch::Tensor> item_weights) {
   check_cuda_f32(Xq, "Xq");
   check_cuda_f32(Y, "Y");
+  const float* wts = check_item_weights(item_weights, Y, prof.has_value());
   const int64_t f = Y.size(1);
   TORCH_CHECK(supported_rank(f), "rank must be one of 16/32/64/128, got ", f);
   TORCH_CHECK(Xq.size(1) == f, "Xq/Y rank mismatch");
@@ -393,7 +414,7 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score(
                     a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
                     out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f,
                     (int)K, (int)n_slices, (int)item_base, a.prof,
-                    a.item_cats, a.query_cats, a.cw, stream);
+                    a.item_cats, a.query_cats, a.cw, wts, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }
@@ -415,13 +436,15 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
     c10::optional<torch::Tensor> prof,
     c10::optional<torch::Tensor> item_cats,
     c10::optional<torch::Tensor> query_cats, bool interleave,
-    c10::optional<bool> gth_opt) {
+    c10::optional<bool> gth_opt,
+    c10::optional<torch::Tensor> item_weights) {
   TORCH_CHECK(Xq.is_cuda() && Xq.is_contiguous() &&
                   Xq.scalar_type() == torch::kBFloat16,
               "Xq must be contiguous bf16 GPU");
   TORCH_CHECK(Y.is_cuda() && Y.is_contiguous() &&
                   Y.scalar_type() == torch::kBFloat16,
               "Y must be contiguous bf16 GPU");
+  const float* wts = check_item_weights(item_weights, Y, prof.has_value());
   const int64_t f = Y.size(1);
   TORCH_CHECK(f == 32 || f == 64 || f == 128,
               "mfma rank must be one of 32/64/128, got ", f);
@@ -465,22 +488,25 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
       a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
       out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f, (int)K,
       (int)n_slices, (int)item_base, a.prof, th_g_ptr, a.item_cats,
-      a.query_cats, a.cw, interleave ? 1 : 0, stream);
+      a.query_cats, a.cw, interleave ? 1 : 0, wts, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
 }
 
-// out[b, c] = dot(Xq[b, :], Y[idx[b, c], :]) in fp32; idx < 0 gives -inf.
+// out[b, c] = dot(Xq[b, :], Y[idx[b, c], :]) in fp32, times
+// item_weights[idx[b, c]] when weights are given; idx < 0 gives -inf.
 // Any rank: rows move as float4 when f % 4 == 0 and both base pointers
 // are 16-byte aligned, as single floats otherwise. The kernel trusts
 // idx, so the upper bound is checked here (one small reduction).
 torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
-                           torch::Tensor idx) {
+                           torch::Tensor idx,
+                           c10::optional<torch::Tensor> item_weights) {
   // idx is int32: checked first, before anything looks at the data
   TORCH_CHECK_VALUE(Y.dim() == 2 && Y.size(0) < (1LL << 31),
                     "the item count N must be below 2^31");
   check_cuda_f32(Xq, "Xq");
   check_cuda_f32(Y, "Y");
+  const float* wts = check_item_weights(item_weights, Y, false);
   TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2 && idx.dim() == 2,
               "Xq, Y and idx must be 2-D");
   TORCH_CHECK(Xq.size(1) == Y.size(1), "Xq/Y rank mismatch");
@@ -502,7 +528,7 @@ torch::Tensor topk_rescore(torch::Tensor Xq, torch::Tensor Y,
   hipStream_t stream =
       c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   launch_topk_rescore(Xq.data_ptr<float>(), Y.data_ptr<float>(),
-                      idx.data_ptr<int>(), out.data_ptr<float>(),
+                      idx.data_ptr<int>(), wts, out.data_ptr<float>(),
                       (long long)B, (int)C, (int)Xq.size(1), stream);
   C10_HIP_CHECK(hipGetLastError());
   return out;
@@ -631,10 +657,12 @@ std::tuple<torch::Tensor, torch::Tensor> topk_cand(
     c10::optional<torch::Tensor> ban_indices,
     c10::optional<torch::Tensor> item_cats,
     c10::optional<torch::Tensor> query_cats,
-    c10::optional<torch::Tensor> scores) {
+    c10::optional<torch::Tensor> scores,
+    c10::optional<torch::Tensor> item_weights) {
   check_cuda_f32(Xq, "Xq");
   check_cuda_f32(Y, "Y");
   TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2, "Xq and Y must be 2-D");
+  const float* wts = check_item_weights(item_weights, Y, false);
   const int64_t B = Xq.size(0);
   const int64_t N = Y.size(0);
   const int64_t f = Y.size(1);
@@ -687,7 +715,7 @@ std::tuple<torch::Tensor, torch::Tensor> topk_cand(
       Xq.data_ptr<float>(), Y.data_ptr<float>(), cand_indices.data_ptr<int>(),
       reinterpret_cast<const long long*>(segs.data_ptr<int64_t>()),
       (int)n_segs, a.mask, a.ban_indptr, a.ban_indices, a.item_cats,
-      a.query_cats, a.cw, (int)f, (int)K, thr, out_val.data_ptr<float>(),
+      a.query_cats, wts, a.cw, (int)f, (int)K, thr, out_val.data_ptr<float>(),
       out_idx.data_ptr<int>(), scores_ptr, (int)grid, stream);
   C10_HIP_CHECK(hipGetLastError());
   return {out_val, out_idx};
@@ -921,7 +949,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
         py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
-        py::arg("query_cats") = py::none());
+        py::arg("query_cats") = py::none(),
+        py::arg("item_weights") = py::none());
   m.def("topk_score_mfma", &topk_score_mfma,
         "Fused masked top-K scoring on MFMA (bf16 in, fp32 accumulate)",
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
@@ -929,10 +958,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
         py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
         py::arg("query_cats") = py::none(), py::arg("interleave") = false,
-        py::arg("gth") = py::none());
+        py::arg("gth") = py::none(), py::arg("item_weights") = py::none());
   m.def("topk_rescore", &topk_rescore,
         "Exact fp32 dots of each query with its shortlisted items",
-        py::arg("Xq"), py::arg("Y"), py::arg("idx"));
+        py::arg("Xq"), py::arg("Y"), py::arg("idx"),
+        py::arg("item_weights") = py::none());
   m.def("cooc_topn", &cooc_topn,
         "Co-occurrence top-N of the listed item rows, one tier",
         py::arg("u_indptr"), py::arg("u_items"), py::arg("i_indptr"),
@@ -948,7 +978,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(),
         py::arg("item_cats") = py::none(), py::arg("query_cats") = py::none(),
-        py::arg("scores") = py::none());
+        py::arg("scores") = py::none(),
+        py::arg("item_weights") = py::none());
   m.def("cooc_dense_lds_max", &cooc_dense_lds_max,
         "Largest item count of the LDS dense tier");
   m.def("indicator_topk", &indicator_topk,

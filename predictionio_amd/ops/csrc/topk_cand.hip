@@ -54,6 +54,16 @@
 // candidate to scores[position], -inf where it is filtered, and selects
 // nothing. The wrapper uses it for K > 64.
 //
+// Item weights (WT): the served score is dot * item_weights[j]. The
+// weight is one more piece of the candidate's metadata: loaded in the
+// trip t + 1 prefetch with the mask byte and the category words, and
+// multiplied in after the butterfly, before the key is formed or the
+// score written. The product plus 0.0f: a zero weight must give +0.0,
+// because ord(-0.0) != ord(+0.0) and the key order would otherwise put a
+// zero score with a negative dot below one with a positive dot. A NaN
+// product is the caller's doing and is not special-cased. WT == false is
+// unchanged.
+//
 // Ids and segments are trusted: the wrapper range-checks the ids and
 // builds the segments itself (a bad id would be an out-of-bounds gather).
 //
@@ -154,14 +164,15 @@ __device__ __forceinline__ void tc_load_row(
   }
 }
 
-// mask byte and category words of one candidate
-template <int CW>
+// mask byte, category words and (WT) weight of one candidate
+template <int CW, bool WT>
 struct TcMeta {
   int banned;
   int c[CW > 0 ? CW : 1];
+  float w[WT ? 1 : 0];
 };
 
-template <int THREADS, bool VEC, int CW, bool SCORES>
+template <int THREADS, bool VEC, int CW, bool SCORES, bool WT>
 __global__ __launch_bounds__(THREADS)
 void topk_cand_kernel(
     const float* __restrict__ Xq,            // B x f
@@ -174,6 +185,7 @@ void topk_cand_kernel(
     const int* __restrict__ ban_indices,
     const int* __restrict__ item_cats,       // N x CW
     const int* __restrict__ query_cats,      // B x CW
+    const float* __restrict__ item_weights,  // N (WT)
     int f, int K,
     float* __restrict__ out_val,             // n_segs x K
     int* __restrict__ out_idx,               // n_segs x K
@@ -222,8 +234,9 @@ void topk_cand_kernel(
 
       const long long last = hi - 1;
       auto fetch_id = [&](long long p) { return cand[p < hi ? p : last]; };
-      auto fetch_meta = [&](int j, TcMeta<CW>& m) {
+      auto fetch_meta = [&](int j, TcMeta<CW, WT>& m) {
         m.banned = item_mask != nullptr ? (int)item_mask[j] : 0;
+        if constexpr (WT) m.w[0] = item_weights[j];
         if constexpr (CW > 0) {
 #pragma unroll
           for (int w = 0; w < CW; ++w)
@@ -234,7 +247,7 @@ void topk_cand_kernel(
       long long p = lo + grp;
       int j0 = fetch_id(p);
       int j1 = fetch_id(p + NG);
-      TcMeta<CW> m0, m1;
+      TcMeta<CW, WT> m0, m1;
       fetch_meta(j0, m0);
 
       for (long long base = lo; base < hi;) {
@@ -270,6 +283,7 @@ void topk_cand_kernel(
           // every lane of the wave takes part, candidate or not
 #pragma unroll
           for (int o = TC_GROUP / 2; o > 0; o >>= 1) sc += __shfl_xor(sc, o);
+          if constexpr (WT) sc = sc * m0.w[0] + 0.0f;
 
           if (sub == 0 && live) {
             if constexpr (SCORES) {
@@ -312,23 +326,31 @@ void topk_cand_kernel(
 
 // threads: 64 or 256. K = 0 selects scores mode (scores != null, always
 // the 256-thread body); otherwise 1 <= K <= TC_KMAX. cw: category words
-// per item, 0 / 1 / 2 / 4. The caller sizes the grid.
+// per item, 0 / 1 / 2 / 4. item_weights: nullptr = unweighted. The caller
+// sizes the grid.
 extern "C" void launch_topk_cand(
     const float* Xq, const float* Y, const int* cand, const long long* segs,
     int n_segs, const uint8_t* item_mask, const long long* ban_indptr,
     const int* ban_indices, const int* item_cats, const int* query_cats,
-    int cw, int f, int K, int threads, float* out_val, int* out_idx,
-    float* scores, int grid, hipStream_t stream)
+    const float* item_weights, int cw, int f, int K, int threads,
+    float* out_val, int* out_idx, float* scores, int grid,
+    hipStream_t stream)
 {
   if (n_segs <= 0 || grid <= 0) return;
   const bool vec = f % 4 == 0 &&
                    reinterpret_cast<uintptr_t>(Xq) % 16 == 0 &&
                    reinterpret_cast<uintptr_t>(Y) % 16 == 0;
-#define TC_LAUNCH(T, V, C, SC)                                             \
-  hipLaunchKernelGGL((topk_cand_kernel<T, V, C, SC>), dim3((unsigned)grid), \
-                     dim3(T), 0, stream, Xq, Y, cand, segs, n_segs,        \
-                     item_mask, ban_indptr, ban_indices, item_cats,        \
-                     query_cats, f, K, out_val, out_idx, scores)
+#define TC_LAUNCH_WT(T, V, C, SC, WT)                                     \
+  hipLaunchKernelGGL((topk_cand_kernel<T, V, C, SC, WT>),                 \
+                     dim3((unsigned)grid), dim3(T), 0, stream, Xq, Y,     \
+                     cand, segs, n_segs, item_mask, ban_indptr,           \
+                     ban_indices, item_cats, query_cats, item_weights, f, \
+                     K, out_val, out_idx, scores)
+#define TC_LAUNCH(T, V, C, SC)                                 \
+  do {                                                         \
+    if (item_weights != nullptr) TC_LAUNCH_WT(T, V, C, SC, true); \
+    else TC_LAUNCH_WT(T, V, C, SC, false);                     \
+  } while (0)
 #define TC_BY_CW(T, V, SC)                 \
   do {                                     \
     if (cw == 0) TC_LAUNCH(T, V, 0, SC);   \
@@ -348,4 +370,5 @@ extern "C" void launch_topk_cand(
   }
 #undef TC_BY_CW
 #undef TC_LAUNCH
+#undef TC_LAUNCH_WT
 }

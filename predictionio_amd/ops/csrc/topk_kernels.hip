@@ -60,7 +60,23 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // becomes -FLT_MAX BEFORE the threshold test (see topk_mfma.hip for why
 // the filter must not wait for the insert path). All CW > 0 code sits
 // under `if constexpr`; CW == 0 is unchanged.
-template <int F, bool PROF, int CW = 0>
+//
+// WT = true multiplies every score by its item's weight (the served score
+// of item j is (Xq[b] . Y[j]) * item_weights[j]): the chunk's TK_CHUNK
+// weights are staged next to the category words, read with one broadcast
+// LDS read per item, and multiplied in BEFORE the tail select, the
+// category select and the threshold test, which all set or compare
+// against -FLT_MAX (times a negative weight: a huge positive score). A
+// zero weight gives +0.0 (the product plus 0.0f); a NaN product fails
+// `s > th` and is never inserted. All WT code sits under `if constexpr`;
+// WT == false is unchanged. The WT = true instantiations are built in a
+// translation unit of their own (topk_kernels_wt.hip includes this file
+// with TK_WT defined).
+#ifndef TK_WT
+#define TK_WT false
+#endif
+
+template <int F, bool PROF, int CW = 0, bool WT = false>
 __global__ __launch_bounds__(256, 3) void topk_score_kernel(
     const float* __restrict__ Xq,        // B x F query vectors
     const float* __restrict__ Y,         // N x F item factors
@@ -72,20 +88,23 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
     int B, long long N, int K, int n_slices, int item_base,
     unsigned long long* prof,
     const int* __restrict__ item_cats,    // N x CW bit words (CW > 0)
-    const int* __restrict__ query_cats)   // B x CW accepted-bit words
+    const int* __restrict__ query_cats,   // B x CW accepted-bit words
+    const float* __restrict__ item_weights)  // N score weights (WT)
 {
   static_assert(CW == 0 || CW == 1 || CW == 2 || CW == 4,
                 "category words per item must be 1, 2 or 4");
   static_assert(CW == 0 || !PROF, "no phase probe with the category filter");
+  static_assert(!WT || !PROF, "no phase probe with item weights");
   constexpr int FP = F + 4;  // row stride: 16B-aligned so the score loop
                              // reads ys rows as ds_read_b128 quads
   // dynamic LDS: ys[TK_CHUNK][FP] | cats[TK_CHUNK][CW] | qc[CW][TK_UPB] |
-  //              topv[TK_WAVES*TK_UPB][K] | topi[...]
+  //              wts[TK_CHUNK] (WT) | topv[TK_WAVES*TK_UPB][K] | topi[...]
   extern __shared__ float lds[];
   float* ys = lds;
   unsigned* cats_lds = reinterpret_cast<unsigned*>(ys + TK_CHUNK * FP);
   unsigned* qc_lds = cats_lds + TK_CHUNK * CW;   // [CW][TK_UPB]
-  float* topv = ys + TK_CHUNK * FP + TK_CHUNK * CW + TK_UPB * CW;
+  float* wts_lds = ys + TK_CHUNK * FP + TK_CHUNK * CW + TK_UPB * CW;
+  float* topv = wts_lds + (WT ? TK_CHUNK : 0);
   int* topi = reinterpret_cast<int*>(topv + TK_WAVES * TK_UPB * (K + 1));
 
   const int tid = threadIdx.x;
@@ -193,6 +212,12 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
       cstg = (it0 + tid / CW < it1)
           ? (unsigned)item_cats[it0 * CW + tid] : 0u;
   }
+  // and so do the weights: thread t < TK_CHUNK carries item t's
+  float wstg = 0.f;
+  if constexpr (WT) {
+    if (PIPE && tid < TK_CHUNK)
+      wstg = (it0 + tid < it1) ? item_weights[it0 + tid] : 0.f;
+  }
   if (PIPE) {
     const int cn0 = (int)min((long long)TK_CHUNK, it1 - it0);
     // uniform chunk base folded into the pointer: the per-thread offset
@@ -233,6 +258,9 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
       if constexpr (CW > 0) {
         if (tid < TK_CHUNK * CW) cats_lds[tid] = cstg;
       }
+      if constexpr (WT) {
+        if (tid < TK_CHUNK) wts_lds[tid] = wstg;
+      }
     } else {
       // coalesced stage of cn item rows
       for (int e = tid; e < cn * F; e += 256) {
@@ -244,6 +272,10 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
         if (tid < TK_CHUNK * CW)
           cats_lds[tid] = (tid / CW < cn)
               ? (unsigned)item_cats[base * CW + tid] : 0u;
+      }
+      if constexpr (WT) {
+        if (tid < TK_CHUNK)
+          wts_lds[tid] = tid < cn ? item_weights[base + tid] : 0.f;
       }
     }
     __syncthreads();
@@ -258,6 +290,10 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
         if (nbase < it1 && tid < TK_CHUNK * CW)
           cstg = (nbase + tid / CW < it1)
               ? (unsigned)item_cats[nbase * CW + tid] : 0u;
+      }
+      if constexpr (WT) {
+        if (nbase < it1 && tid < TK_CHUNK)
+          wstg = (nbase + tid < it1) ? item_weights[nbase + tid] : 0.f;
       }
       if (nbase < it1) {
         const int cnn = (int)min((long long)TK_CHUNK, it1 - nbase);
@@ -316,7 +352,11 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
       for (int g = 0; g < GRP; ++g) {
       const int c = c0 + g;
       const long long item = base + c;
-      float s = g < gn ? sg[g] : -FLT_MAX;
+      float s = sg[g];
+      // weight first (one broadcast read; row c < TK_CHUNK always), then
+      // the selects that produce -FLT_MAX
+      if constexpr (WT) s = s * wts_lds[c] + 0.0f;
+      s = g < gn ? s : -FLT_MAX;
       if constexpr (CW > 0) {
         // one broadcast LDS read per word (c is wave-uniform)
         unsigned hit = 0u;
@@ -377,10 +417,11 @@ __global__ __launch_bounds__(256, 3) void topk_score_kernel(
 // Dynamic LDS of topk_score_kernel<f, *, cw> (layout at the top of its
 // body), floored for small K by the query-staging pass, which writes
 // TK_UPB rows of ys before the lists are initialized.
-constexpr size_t tk_lds_bytes(int f, int K, int cw) {
+constexpr size_t tk_lds_bytes(int f, int K, int cw, bool wt) {
   const size_t need =
       sizeof(float) * (TK_CHUNK * (f + 4)) +
       sizeof(int) * (TK_CHUNK + TK_UPB) * cw +
+      (wt ? sizeof(float) * TK_CHUNK : 0) +
       (sizeof(float) + sizeof(int)) * TK_WAVES * TK_UPB * (K + 1);
   const size_t stage_need = sizeof(float) * TK_UPB * (f + 4);
   return need < stage_need ? stage_need : need;
@@ -389,17 +430,23 @@ constexpr size_t tk_lds_bytes(int f, int K, int cw) {
 // args = the kernel's arguments, in order
 template <int F, bool PROF, int CW, typename... Args>
 static void launch(dim3 grid, int K, hipStream_t stream, Args... args) {
-  launch_dyn_lds<topk_score_kernel<F, PROF, CW>>(
-      grid, dim3(256), tk_lds_bytes(F, K, CW), stream, args...);
+  launch_dyn_lds<topk_score_kernel<F, PROF, CW, TK_WT>>(
+      grid, dim3(256), tk_lds_bytes(F, K, CW, TK_WT), stream, args...);
 }
 
-// the binding rejects prof together with a category filter
+// the binding rejects prof together with a category filter or with item
+// weights
 template <int F, typename... Args>
 static void launch_rank(bool prof, int cw, Args... args) {
   switch (cw) {
     case 0:
-      if (prof) launch<F, true, 0>(args...);
-      else launch<F, false, 0>(args...);
+      if constexpr (!TK_WT) {
+        if (prof) {
+          launch<F, true, 0>(args...);
+          break;
+        }
+      }
+      launch<F, false, 0>(args...);
       break;
     case 1: launch<F, false, 1>(args...); break;
     case 2: launch<F, false, 2>(args...); break;
@@ -408,15 +455,39 @@ static void launch_rank(bool prof, int cw, Args... args) {
   }
 }
 
-extern "C" void launch_topk_score(
+#if TK_WT
+#define TK_ENTRY launch_topk_score_wt
+#else
+#define TK_ENTRY launch_topk_score
+// the WT = true instantiations (topk_kernels_wt.hip)
+extern "C" void launch_topk_score_wt(
     const float* Xq, const float* Y, const uint8_t* item_mask,
     const long long* ban_indptr, const int* ban_indices,
     float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof,
     const int* item_cats, const int* query_cats, int cw,
-    hipStream_t stream)
+    const float* item_weights, hipStream_t stream);
+#endif
+
+// item_weights: nullptr = unweighted
+extern "C" void TK_ENTRY(
+    const float* Xq, const float* Y, const uint8_t* item_mask,
+    const long long* ban_indptr, const int* ban_indices,
+    float* out_val, int* out_idx,
+    int B, long long N, int f, int K, int n_slices, int item_base,
+    unsigned long long* prof,
+    const int* item_cats, const int* query_cats, int cw,
+    const float* item_weights, hipStream_t stream)
 {
+#if !TK_WT
+  if (item_weights != nullptr) {
+    launch_topk_score_wt(Xq, Y, item_mask, ban_indptr, ban_indices, out_val,
+                         out_idx, B, N, f, K, n_slices, item_base, prof,
+                         item_cats, query_cats, cw, item_weights, stream);
+    return;
+  }
+#endif
   const dim3 grid(n_slices, (B + TK_UPB - 1) / TK_UPB);
   // the rank arrives as a compile-time tag so the argument list is
   // written once
@@ -424,7 +495,7 @@ extern "C" void launch_topk_score(
     launch_rank<decltype(rank)::value>(
         prof != nullptr, cw, grid, K, stream, Xq, Y, item_mask, ban_indptr,
         ban_indices, out_val, out_idx, B, N, K, n_slices, item_base, prof,
-        item_cats, query_cats);
+        item_cats, query_cats, item_weights);
   };
   switch (f) {
     case 16: go(std::integral_constant<int, 16>{}); break;

@@ -75,15 +75,17 @@ constexpr int tm_cats_stride(int cw) {
 // Dynamic LDS layout, in order (KP = K + 1):
 //   ys     [TM_CHUNK][F]          bf16  staged Y chunk (swizzled)
 //   cats   [CW][tm_cats_stride]   u32   staged item category words
+//   wts    [TM_CHUNK]             f32   staged item weights (WT only)
 //   topv   [TM_UPB][KP]           f32   per-query top-K values
 //   topi   [TM_UPB][KP]           i32   per-query top-K items
 //   th     [TM_UPB]               f32   per-query K-th-best threshold
 //   qc     [CW][TM_UPB]           u32   per-query accepted words
-// At most 52 KB (F=128, K=64, CW=4). ops/topk.py sizes n_slices from the
-// same sum.
-constexpr size_t tm_lds_bytes(int f, int K, int cw) {
+// At most 52 KB (F=128, K=64, CW=4, WT). ops/topk.py sizes n_slices from
+// the same sum.
+constexpr size_t tm_lds_bytes(int f, int K, int cw, bool wt) {
   return (size_t)TM_CHUNK * (f * 2) +
          (size_t)cw * tm_cats_stride(cw) * 4 +
+         (wt ? sizeof(float) * TM_CHUNK : 0) +
          (sizeof(float) + sizeof(int)) * TM_UPB * (K + 1) +
          sizeof(float) * TM_UPB + sizeof(int) * TM_UPB * cw;
 }
@@ -127,7 +129,25 @@ __device__ __forceinline__ float tm_dec(unsigned k) {
 // would hold far more than its share of a query's best items. A slice
 // past the last chunk loads nothing and writes K empty slots. Every ILV
 // line is a compile-time branch; ILV == false is unchanged.
-template <int F, bool PROF, int CW = 0, bool ILV = false>
+//
+// WT = true multiplies every score by its item's weight: the served score
+// of item j is (Xq[b] . Y[j]) * item_weights[j], and the lists, the
+// thresholds and the cross-slice exchange all hold that product. The
+// chunk's TM_CHUNK fp32 weights ride the staging pipeline next to the
+// category words (a second staging register on threads 0..63: with CW = 4
+// every thread already carries a category word) into one LDS row, and a
+// lane reads the weights of its four D rows as one b128 per item fragment.
+// The multiply sits BEFORE the category select: -FLT_MAX times a negative
+// weight would be a huge positive score. A zero weight gives +0.0 (the
+// product plus 0.0f). A NaN product fails `s > th` and is never inserted.
+// Every WT line is a compile-time branch; WT == false is unchanged. The
+// WT = true instantiations are built in a translation unit of their own
+// (topk_mfma_wt.hip includes this file with TM_WT defined).
+#ifndef TM_WT
+#define TM_WT false
+#endif
+
+template <int F, bool PROF, int CW = 0, bool ILV = false, bool WT = false>
 __global__ __launch_bounds__(TM_BS, 6)
 void topk_mfma_kernel(
     const unsigned short* __restrict__ Xq,   // B x F bf16
@@ -146,12 +166,14 @@ void topk_mfma_kernel(
     unsigned* __restrict__ th_g,
     int kflags,  // bit 0: disable the ban bloom (A/B hook)
     const int* __restrict__ item_cats,   // N x CW bit words (CW > 0)
-    const int* __restrict__ query_cats)  // B x CW accepted-bit words
+    const int* __restrict__ query_cats,  // B x CW accepted-bit words
+    const float* __restrict__ item_weights)  // N score weights (WT)
 {
   static_assert(CW == 0 || CW == 1 || CW == 2 || CW == 4,
                 "category words per item must be 1, 2 or 4");
   static_assert(CW == 0 || !PROF, "no phase probe with the category filter");
   static_assert(!ILV || !PROF, "no phase probe with interleaved slices");
+  static_assert(!WT || !PROF, "no phase probe with item weights");
   static_assert(TM_CHUNK * CW <= TM_BS,
                 "one staged category word per thread");
   constexpr int ROWB = F * 2;            // bytes per staged Y row
@@ -163,8 +185,9 @@ void topk_mfma_kernel(
   extern __shared__ char lds_raw[];
   unsigned short* ys = reinterpret_cast<unsigned short*>(lds_raw);
   unsigned* cats_lds = reinterpret_cast<unsigned*>(lds_raw + TM_CHUNK * ROWB);
-  float* topv = reinterpret_cast<float*>(
+  float* wts_lds = reinterpret_cast<float*>(
       lds_raw + TM_CHUNK * ROWB + CW * CSTR * 4);
+  float* topv = wts_lds + (WT ? TM_CHUNK : 0);
   const int KP = K + 1;  // stride coprime with the 32 banks
   int* topi = reinterpret_cast<int*>(topv + TM_UPB * KP);
   float* th_lds = reinterpret_cast<float*>(topi + TM_UPB * KP);
@@ -276,7 +299,14 @@ void topk_mfma_kernel(
   // the word-major LDS image on drain. Rows at or past it1 stage 0 =
   // "filtered", which also covers the tail chunk.
   unsigned cstg = 0u;
+  // weight staging: thread t < TM_CHUNK carries the weight of the chunk's
+  // item t; rows at or past it1 stage 0
+  float wstg = 0.f;
   auto load_stg = [&](long long cbase) {
+    if constexpr (WT) {
+      if (tid < TM_CHUNK)
+        wstg = (cbase + tid < it1) ? item_weights[cbase + tid] : 0.f;
+    }
     if constexpr (CW > 0) {
       if (tid < TM_CHUNK * CW)
         cstg = (cbase + tid / CW < it1)
@@ -307,6 +337,9 @@ void topk_mfma_kernel(
     }
     if constexpr (CW > 0) {
       if (tid < TM_CHUNK * CW) cats_lds[(tid % CW) * CSTR + tid / CW] = cstg;
+    }
+    if constexpr (WT) {
+      if (tid < TM_CHUNK) wts_lds[tid] = wstg;
     }
   };
   // pipelined cross-slice threshold: the register holds the value read
@@ -378,6 +411,18 @@ void topk_mfma_kernel(
             row * ROWB + (col ^ ((row & SWM) << 4)));
         acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a, xf[ks], acc[i], 0, 0, 0);
+      }
+    }
+
+    // ---- item weights, ahead of the category select (see WT above):
+    // the lane's D rows i*16 + lg*4 + r are contiguous in wts_lds
+    if constexpr (WT) {
+#pragma unroll
+      for (int i = 0; i < IFR; ++i) {
+        const f32x4 w =
+            *reinterpret_cast<const f32x4*>(&wts_lds[i * 16 + lg * 4]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][r] = acc[i][r] * w[r] + 0.0f;
       }
     }
 
@@ -500,8 +545,8 @@ void topk_mfma_kernel(
 // args = the kernel's arguments, in order
 template <int F, bool PROF, int CW, bool ILV, typename... Args>
 static void launch(dim3 grid, int K, hipStream_t stream, Args... args) {
-  launch_dyn_lds<topk_mfma_kernel<F, PROF, CW, ILV>>(
-      grid, dim3(TM_BS), tm_lds_bytes(F, K, CW), stream, args...);
+  launch_dyn_lds<topk_mfma_kernel<F, PROF, CW, ILV, TM_WT>>(
+      grid, dim3(TM_BS), tm_lds_bytes(F, K, CW, TM_WT), stream, args...);
 }
 
 template <int F, int CW, typename... Args>
@@ -510,14 +555,19 @@ static void launch_cw(bool ilv, Args... args) {
   else launch<F, false, CW, false>(args...);
 }
 
-// the binding rejects prof together with a category filter or with
-// interleaved slices
+// the binding rejects prof together with a category filter, with
+// interleaved slices or with item weights
 template <int F, typename... Args>
 static void launch_rank(bool prof, int cw, bool ilv, Args... args) {
   switch (cw) {
     case 0:
-      if (prof) launch<F, true, 0, false>(args...);
-      else launch_cw<F, 0>(ilv, args...);
+      if constexpr (!TM_WT) {
+        if (prof) {
+          launch<F, true, 0, false>(args...);
+          break;
+        }
+      }
+      launch_cw<F, 0>(ilv, args...);
       break;
     case 1: launch_cw<F, 1>(ilv, args...); break;
     case 2: launch_cw<F, 2>(ilv, args...); break;
@@ -526,15 +576,40 @@ static void launch_rank(bool prof, int cw, bool ilv, Args... args) {
   }
 }
 
-extern "C" void launch_topk_mfma(
+#if TM_WT
+#define TM_ENTRY launch_topk_mfma_wt
+#else
+#define TM_ENTRY launch_topk_mfma
+// the WT = true instantiations (topk_mfma_wt.hip)
+extern "C" void launch_topk_mfma_wt(
     const unsigned short* Xq, const unsigned short* Y,
     const uint8_t* item_mask, const long long* ban_indptr,
     const int* ban_indices, float* out_val, int* out_idx,
     int B, long long N, int f, int K, int n_slices, int item_base,
     unsigned long long* prof, unsigned* th_g,
     const int* item_cats, const int* query_cats, int cw, int interleave,
-    hipStream_t stream)
+    const float* item_weights, hipStream_t stream);
+#endif
+
+// item_weights: nullptr = unweighted
+extern "C" void TM_ENTRY(
+    const unsigned short* Xq, const unsigned short* Y,
+    const uint8_t* item_mask, const long long* ban_indptr,
+    const int* ban_indices, float* out_val, int* out_idx,
+    int B, long long N, int f, int K, int n_slices, int item_base,
+    unsigned long long* prof, unsigned* th_g,
+    const int* item_cats, const int* query_cats, int cw, int interleave,
+    const float* item_weights, hipStream_t stream)
 {
+#if !TM_WT
+  if (item_weights != nullptr) {
+    launch_topk_mfma_wt(Xq, Y, item_mask, ban_indptr, ban_indices, out_val,
+                        out_idx, B, N, f, K, n_slices, item_base, prof, th_g,
+                        item_cats, query_cats, cw, interleave, item_weights,
+                        stream);
+    return;
+  }
+#endif
   const dim3 grid((B + TM_UPB - 1) / TM_UPB, n_slices);
   const char* e_bl = getenv("PIO_TOPK_BLOOM");
   const int kflags = (e_bl != nullptr && e_bl[0] == '0') ? 1 : 0;
@@ -544,7 +619,8 @@ extern "C" void launch_topk_mfma(
     launch_rank<decltype(rank)::value>(
         prof != nullptr, cw, interleave != 0, grid, K, stream, Xq, Y,
         item_mask, ban_indptr, ban_indices, out_val, out_idx, B, N, K,
-        n_slices, item_base, prof, th_g, kflags, item_cats, query_cats);
+        n_slices, item_base, prof, th_g, kflags, item_cats, query_cats,
+        item_weights);
   };
   switch (f) {
     case 32: go(std::integral_constant<int, 32>{}); break;

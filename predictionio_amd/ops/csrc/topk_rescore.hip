@@ -2,6 +2,9 @@
 //
 //   out[b, c] = dot(Xq[b, :], Y[idx[b, c], :])      idx [B, C] int32
 //
+// times w[idx[b, c]] when per-item score weights are given (the product
+// plus 0.0f, so a zero weight gives +0.0 whatever the dot's sign).
+//
 // The union path for K > 64 (ops/topk.py) shortlists C = 2K candidates
 // per query on their bf16 scores and needs their exact fp32 dots. Doing
 // that as a gather Y[idx] plus an einsum materializes a B x C x f fp32
@@ -28,6 +31,7 @@ void topk_rescore_kernel(
     const float* __restrict__ Xq,   // B x f
     const float* __restrict__ Y,    // N x f
     const int* __restrict__ idx,    // B x C
+    const float* __restrict__ w,    // N score weights, or nullptr
     float* __restrict__ out,        // B x C
     long long total,                // B * C
     int C, int f)
@@ -57,12 +61,15 @@ void topk_rescore_kernel(
   // every lane of the wave takes part, live or not
 #pragma unroll
   for (int o = RS_GROUP / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if (live && sub == 0) out[cand] = j >= 0 ? acc : -INFINITY;
+  if (live && sub == 0) {
+    if (j >= 0 && w != nullptr) acc = acc * w[j] + 0.0f;
+    out[cand] = j >= 0 ? acc : -INFINITY;
+  }
 }
 
 extern "C" void launch_topk_rescore(
-    const float* Xq, const float* Y, const int* idx, float* out,
-    long long B, int C, int f, hipStream_t stream)
+    const float* Xq, const float* Y, const int* idx, const float* w,
+    float* out, long long B, int C, int f, hipStream_t stream)
 {
   const long long total = B * C;
   if (total == 0) return;
@@ -72,8 +79,8 @@ extern "C" void launch_topk_rescore(
                    reinterpret_cast<uintptr_t>(Y) % 16 == 0;
   if (vec)
     hipLaunchKernelGGL(topk_rescore_kernel<true>, dim3((unsigned)blocks),
-                       dim3(RS_BS), 0, stream, Xq, Y, idx, out, total, C, f);
+                       dim3(RS_BS), 0, stream, Xq, Y, idx, w, out, total, C, f);
   else
     hipLaunchKernelGGL(topk_rescore_kernel<false>, dim3((unsigned)blocks),
-                       dim3(RS_BS), 0, stream, Xq, Y, idx, out, total, C, f);
+                       dim3(RS_BS), 0, stream, Xq, Y, idx, w, out, total, C, f);
 }

@@ -60,7 +60,8 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                query_cats: Optional[torch.Tensor] = None,
                list_k: Optional[int] = None,
                cand_indptr: Optional[torch.Tensor] = None,
-               cand_indices: Optional[torch.Tensor] = None
+               cand_indices: Optional[torch.Tensor] = None,
+               item_weights: Optional[torch.Tensor] = None
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K of (Xq @ Y.T) per query row, with optional global item mask
     (uint8, 1=banned) and per-query banned lists (CSR int32, sorted).
@@ -97,19 +98,36 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     candidate list: only the listed rows of Y are read, the three filters
     apply as above, and the result is exact fp32 in the order score
     descending, id ascending on equal scores (_topk_score_cands on GPU
-    in every mode, topk_score_cands_ref on CPU)."""
+    in every mode, topk_score_cands_ref on CPU).
+
+    item_weights (contiguous fp32 [N] on the device of Y, shared by the
+    batch) makes the served score of item j for query b
+    (Xq[b] . Y[j]) * item_weights[j]: ranking, returned values, the
+    cross-slice threshold, the shortlist depth and the tie rule are all
+    defined on that product, in every route and under every filter above
+    (an item must still pass them all). With weights the "mfma" contract
+    reads: an item of the top K is served whenever its weighted bf16 rank
+    among the valid items is at most D. Any finite weight is allowed: a
+    negative one flips the score's sign, a zero one gives the score +0.0
+    (never -0.0) and is no filter. Non-finite weights are the caller's
+    responsibility and are not checked: an item whose score is NaN is
+    never inserted by the fused kernels. A tensor of the wrong dtype,
+    shape, layout or device raises ValueError; None changes nothing."""
     B, f = Xq.shape
     N = Y.shape[0]
     K = int(K)
     check_row_count(Xq=B, Y=N)
     _check_cats(item_cats, query_cats, B, N)
+    _check_weights(item_weights, Y)
+    wt = item_weights
     if (cand_indptr is None) != (cand_indices is None):
         raise ValueError(
             "cand_indptr and cand_indices must be given together")
     if cand_indptr is not None:
         fn = _topk_score_cands if Xq.is_cuda else topk_score_cands_ref
         return fn(Xq, Y, K, cand_indptr, cand_indices, item_mask,
-                  ban_indptr, ban_indices, item_cats, query_cats)
+                  ban_indptr, ban_indices, item_cats, query_cats,
+                  item_weights=wt)
     if Xq.is_cuda:
         if mode is None:
             mode = os.environ.get("PIO_TOPK_MODE", "mfma")
@@ -118,7 +136,7 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                 raise ValueError("K must be >= 1")
             out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
                                     ban_indices, n_slices, list_k,
-                                    item_cats, query_cats)
+                                    item_cats, query_cats, wt)
             if out is None:
                 raise ValueError(
                     f"no union plan for B={B}, N={N}, rank={f}, K={K}")
@@ -133,18 +151,18 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                 and not torch.cuda.is_current_stream_capturing()):
             out = _topk_score_union(Xq, Y, K, item_mask, ban_indptr,
                                     ban_indices, n_slices, list_k,
-                                    item_cats, query_cats)
+                                    item_cats, query_cats, wt)
             if out is not None:
                 return out
         if K > 64:
             # arbitrary `num` (the reference allows any): a materialized
             # masked matmul + torch.topk on device
             return _topk_torch_gpu(Xq, Y, K, item_mask, ban_indptr,
-                                   ban_indices, item_cats, query_cats)
+                                   ban_indices, item_cats, query_cats, wt)
         if mode == "mfma" and _mfma_rank(f) is not None:
             return _topk_score_mfma(Xq, Y, K, item_mask, ban_indptr,
                                     ban_indices, n_slices,
-                                    item_cats, query_cats)
+                                    item_cats, query_cats, wt)
         from predictionio_amd.ops import hip_ext
         pf = pad_rank(f)
         Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
@@ -161,7 +179,7 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
             item_mask.contiguous() if item_mask is not None else None,
             ban_indptr.contiguous() if ban_indptr is not None else None,
             ban_indices.contiguous() if ban_indices is not None else None, 0,
-            item_cats=item_cats, query_cats=query_cats)
+            item_cats=item_cats, query_cats=query_cats, item_weights=wt)
         # phase 2: merge per-slice candidates (small [B, n_slices*K] topk)
         mvals, pos = torch.topk(vals, K, dim=1)
         midx = torch.gather(idxs, 1, pos).long()
@@ -172,7 +190,31 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         mvals = mvals.masked_fill(empty, float("-inf"))
         return mvals, midx
     return topk_score_ref(Xq, Y, K, item_mask, ban_indptr, ban_indices,
-                          item_cats, query_cats)
+                          item_cats, query_cats, item_weights=wt)
+
+
+def _check_weights(item_weights, Y: torch.Tensor) -> None:
+    """The item_weights contract (the native binding re-validates it):
+    contiguous fp32 [N] on the device of Y. A mismatch raises — there is
+    no fallback. Values are not looked at (no per-call reduction)."""
+    w = item_weights
+    if w is None:
+        return
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32:
+        raise ValueError("item_weights must be an fp32 tensor")
+    if w.dim() != 1 or w.shape[0] != Y.shape[0]:
+        raise ValueError(f"item_weights must have shape [{Y.shape[0]}], "
+                         f"got {list(w.shape)}")
+    if not w.is_contiguous():
+        raise ValueError("item_weights must be contiguous")
+    if w.device != Y.device:
+        raise ValueError("item_weights must be on the device of Y")
+
+
+def _weighted(scores: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """scores * w as the kernels form it: plus 0.0, so a zero weight
+    gives +0.0 whatever the sign of the raw score."""
+    return scores * w + 0.0
 
 
 def _check_cats(item_cats, query_cats, B: int, N: int) -> None:
@@ -210,13 +252,15 @@ def _cats_miss(item_cats: torch.Tensor, query_cats: torch.Tensor
 
 def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                     item_mask, ban_indptr, ban_indices,
-                    item_cats=None, query_cats=None
+                    item_cats=None, query_cats=None, item_weights=None
                     ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Device fallback for K above what the fused paths take (K > 1024,
     shapes without a union plan, flagged union queries): materialized
     masked score matrix + torch.topk. Memory: B x N fp32 — callers with
     huge B should batch."""
     scores = Xq @ Y.t()
+    if item_weights is not None:  # before the filters write -inf
+        scores = _weighted(scores, item_weights.unsqueeze(0))
     if item_cats is not None:
         scores = scores.masked_fill(_cats_miss(item_cats, query_cats),
                                     float("-inf"))
@@ -244,13 +288,14 @@ def _topk_torch_gpu(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     return vals, idxs
 
 
-def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int) -> int:
+def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int,
+                         wt: bool = False) -> int:
     """Item slices for the MFMA kernel: just enough to fill the chip
     ONCE. The resident-WG count depends on the kernel's LDS (64-item
     tile + the per-query top-K lists), so the target shrinks for large
     K — a 1536-WG grid at K=64 only fits 768 at a time and the second
     pass doubled the time (profiles/serve_k_sweep_r2.log). W = category
-    words per item (0 = no filter)."""
+    words per item (0 = no filter); wt = item weights are staged."""
     ublocks = (B + 63) // 64
     # the kernel's dynamic LDS: tm_lds_bytes in csrc/topk_mfma.hip
     lds = 64 * 2 * pf + 8 * 64 * (K + 1) + 4 * 64
@@ -258,6 +303,8 @@ def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int) -> int:
         # staged item category words (rows padded by 32/W words for
         # W > 1) + the queries' accepted words
         lds += W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
+    if wt:
+        lds += 64 * 4   # the staged weight row
     target = 256 * max(1, min(6, (160 * 1024) // lds))
     return max(2, min(target // ublocks, (N + 255) // 256))
 
@@ -292,7 +339,7 @@ def _union_min_slices(L: int, M: int) -> int:
 
 def _union_plan(B: int, N: int, pf: int, K: int, W: int,
                 list_k: Optional[int] = None,
-                n_slices: Optional[int] = None
+                n_slices: Optional[int] = None, wt: bool = False
                 ) -> Optional[Tuple[int, int]]:
     """(L, S) for the union path: per-slice list length L <= 64 and slice
     count S, or None when the shape admits none (tiny N).
@@ -324,7 +371,7 @@ def _union_plan(B: int, N: int, pf: int, K: int, W: int,
             if _union_rule(L, n_slices, M):
                 return L, n_slices
             continue
-        S = max(2, _mfma_default_slices(B, N, pf, L, W),
+        S = max(2, _mfma_default_slices(B, N, pf, L, W, wt),
                 _union_min_slices(L, M))
         if S <= nch:
             return L, S
@@ -379,7 +426,7 @@ def _select_csr(indptr: torch.Tensor, indices: torch.Tensor,
 def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                       item_mask, ban_indptr, ban_indices,
                       n_slices: Optional[int], list_k: Optional[int],
-                      item_cats=None, query_cats=None
+                      item_cats=None, query_cats=None, item_weights=None
                       ) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
     """Union path, the eager route at every K <= 1024: ONE MFMA launch
     with short lists (L <= 64, the kernel's tuned regime) over S slices
@@ -397,7 +444,8 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     if pf is None or B == 0:
         return None
     W = item_cats.shape[1] if item_cats is not None else 0
-    plan = _union_plan(B, N, pf, K, W, list_k, n_slices)
+    plan = _union_plan(B, N, pf, K, W, list_k, n_slices,
+                       item_weights is not None)
     if plan is None:
         return None
     L, S = plan
@@ -410,9 +458,9 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         ban_indptr.contiguous() if ban_indptr is not None else None,
         ban_indices.contiguous() if ban_indices is not None else None, 0,
         item_cats=item_cats, query_cats=query_cats,
-        interleave=True, gth=False)
+        interleave=True, gth=False, item_weights=item_weights)
     short_idx, _, flagged = _union_merge(vals, idxs, L, S, M)
-    exact = topk_rescore(Xq, Y, short_idx.to(torch.int32))
+    exact = topk_rescore(Xq, Y, short_idx.to(torch.int32), item_weights)
     mv, p2 = torch.topk(exact, min(K, exact.shape[1]), dim=1)
     midx = torch.gather(short_idx, 1, p2)
     midx[mv == float("-inf")] = -1
@@ -441,26 +489,31 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                 bp, bi = _select_csr(ban_indptr, ban_indices, r)
             fv, fi = _topk_torch_gpu(
                 Xq[r], Y, K, item_mask, bp, bi, item_cats,
-                query_cats[r] if query_cats is not None else None)
+                query_cats[r] if query_cats is not None else None,
+                item_weights)
             mv[r] = fv
             midx[r] = fi
     return mv, midx
 
 
-def topk_rescore(Xq: torch.Tensor, Y: torch.Tensor,
-                 idx: torch.Tensor) -> torch.Tensor:
+def topk_rescore(Xq: torch.Tensor, Y: torch.Tensor, idx: torch.Tensor,
+                 item_weights: Optional[torch.Tensor] = None
+                 ) -> torch.Tensor:
     """out[b, c] = Xq[b] . Y[idx[b, c]] in fp32 on the GPU
-    (csrc/topk_rescore.hip), -inf where idx < 0. idx [B, C] int32; Xq and
-    Y are read where they lie."""
+    (csrc/topk_rescore.hip), times item_weights[idx[b, c]] when weights
+    are given; -inf where idx < 0. idx [B, C] int32; Xq and Y are read
+    where they lie."""
     check_row_count(Xq=Xq.shape[0], Y=Y.shape[0])
+    _check_weights(item_weights, Y)
     from predictionio_amd.ops import hip_ext
-    return hip_ext().topk_rescore(Xq.contiguous(), Y.contiguous(), idx)
+    return hip_ext().topk_rescore(Xq.contiguous(), Y.contiguous(), idx,
+                                  item_weights=item_weights)
 
 
 def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                      item_mask, ban_indptr, ban_indices,
                      n_slices: Optional[int],
-                     item_cats=None, query_cats=None
+                     item_cats=None, query_cats=None, item_weights=None
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     """List-kernel MFMA path (capture-safe, any N): bf16 matrix-core
     scoring keeps a list of D = min(2K, 64) per item slice per query
@@ -488,7 +541,8 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     depth = min(2 * K, 64)
     if n_slices is None:
         W = item_cats.shape[1] if item_cats is not None else 0
-        n_slices = _mfma_default_slices(B, N, pf, depth, W)
+        n_slices = _mfma_default_slices(B, N, pf, depth, W,
+                                        item_weights is not None)
     # Y's bf16 copy is cached (factors are static across serving batches);
     # Xq is cast per call — it changes every batch, and under hipGraph
     # capture (GraphedTopK) the cast must be part of the captured work
@@ -498,7 +552,8 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         item_mask.contiguous() if item_mask is not None else None,
         ban_indptr.contiguous() if ban_indptr is not None else None,
         ban_indices.contiguous() if ban_indices is not None else None, 0,
-        item_cats=item_cats, query_cats=query_cats)
+        item_cats=item_cats, query_cats=query_cats,
+        item_weights=item_weights)
     # merge candidate groups down to a 2K shortlist on the bf16 scores
     C = min(vals.shape[1], 2 * K)
     cv, pos = torch.topk(vals, C, dim=1)
@@ -507,6 +562,8 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     # exact fp32 re-score of the shortlist (tiny gather + batched dot)
     Yc = Y[cidx.clamp_min(0)]                      # B x C x f fp32
     exact = torch.einsum("bf,bcf->bc", Xq, Yc)
+    if item_weights is not None:
+        exact = _weighted(exact, item_weights[cidx.clamp_min(0)])
     exact = exact.masked_fill(~valid, float("-inf"))
     mv, p2 = torch.topk(exact, min(K, C), dim=1)
     midx = torch.gather(cidx, 1, p2)
@@ -612,8 +669,8 @@ def _topk_score_cands(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                       cand_indptr: torch.Tensor, cand_indices: torch.Tensor,
                       item_mask=None, ban_indptr=None, ban_indices=None,
                       item_cats=None, query_cats=None,
-                      seg_len: int = 8192, wave_max: int = 256
-                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+                      seg_len: int = 8192, wave_max: int = 256,
+                      item_weights=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Candidate-list top-K on the GPU (csrc/topk_cand.hip): every query
     ranks its own CSR list, reading only the listed rows of Y. Exact
     fp32; order score descending, id ascending. Xq and Y are read where
@@ -669,7 +726,8 @@ def _topk_score_cands(Xq: torch.Tensor, Y: torch.Tensor, K: int,
         else None,
         ban_indices=ban_indices.contiguous() if ban_indices is not None
         else None,
-        item_cats=item_cats, query_cats=query_cats)
+        item_cats=item_cats, query_cats=query_cats,
+        item_weights=item_weights)
     ext = hip_ext()
     ci = cand_indices.contiguous()
     if K > 64:
@@ -698,7 +756,7 @@ def _topk_score_cands(Xq: torch.Tensor, Y: torch.Tensor, K: int,
 
 def topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
                          item_mask=None, ban_indptr=None, ban_indices=None,
-                         item_cats=None, query_cats=None
+                         item_cats=None, query_cats=None, item_weights=None
                          ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch candidate-list top-K (CPU path + GPU numerics
     baseline): gather the candidate rows, score, filter, and order by
@@ -709,12 +767,15 @@ def topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
     if K < 1:
         raise ValueError("K must be >= 1")
     _check_cats(item_cats, query_cats, B, N)
+    _check_weights(item_weights, Y)
     lens, _, _, _ = _check_cands(cand_indptr, cand_indices, B, N,
                                  1 << 62, 1 << 62)
     dev = Xq.device
     qid = torch.repeat_interleave(torch.arange(B, device=dev), lens)
     j = cand_indices.long()
     score = (Xq.float()[qid] * Y.float()[j]).sum(dim=1)
+    if item_weights is not None:
+        score = _weighted(score, item_weights[j])
     ok = torch.ones_like(j, dtype=torch.bool)
     if item_mask is not None:
         ok &= ~item_mask.bool()[j]
@@ -730,7 +791,7 @@ def topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
 
 def topk_score_ref(Xq, Y, K, item_mask=None, ban_indptr=None,
                    ban_indices=None, item_cats=None, query_cats=None,
-                   cand_indptr=None, cand_indices=None
+                   cand_indptr=None, cand_indices=None, item_weights=None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Pure-torch reference (CPU path + GPU numerics baseline)."""
     check_row_count(Xq=Xq.shape[0], Y=Y.shape[0])
@@ -740,9 +801,12 @@ def topk_score_ref(Xq, Y, K, item_mask=None, ban_indptr=None,
     if cand_indptr is not None:
         return topk_score_cands_ref(Xq, Y, K, cand_indptr, cand_indices,
                                     item_mask, ban_indptr, ban_indices,
-                                    item_cats, query_cats)
+                                    item_cats, query_cats, item_weights)
     _check_cats(item_cats, query_cats, Xq.shape[0], Y.shape[0])
+    _check_weights(item_weights, Y)
     scores = Xq.float() @ Y.float().t()  # B x N
+    if item_weights is not None:  # before the filters write -inf
+        scores = _weighted(scores, item_weights.unsqueeze(0))
     if item_cats is not None:
         scores = scores.masked_fill(_cats_miss(item_cats, query_cats),
                                     float("-inf"))

@@ -24,7 +24,8 @@ def sharded_topk_score(Xq: torch.Tensor, Y_local: torch.Tensor, K: int,
                        ban_indptr: Optional[torch.Tensor] = None,
                        ban_indices: Optional[torch.Tensor] = None,
                        item_cats: Optional[torch.Tensor] = None,
-                       query_cats: Optional[torch.Tensor] = None
+                       query_cats: Optional[torch.Tensor] = None,
+                       item_weights: Optional[torch.Tensor] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K over the UNION of all ranks' item shards.
 
@@ -32,7 +33,8 @@ def sharded_topk_score(Xq: torch.Tensor, Y_local: torch.Tensor, K: int,
     this rank's item rows, whose global ids start at `item_base`. Ban
     lists are in LOCAL shard coordinates. The optional category filter
     follows the same split: `item_cats` is row-sharded like `Y_local`,
-    `query_cats` is replicated like `Xq`. Returns (values, global
+    `query_cats` is replicated like `Xq`; `item_weights` is row-sharded
+    like `Y_local` too (this rank's [N_local] slice). Returns (values, global
     indices) identical on every rank. It does not take candidate lists
     (`topk_score(..., cand_indptr=, cand_indices=)`): a list would have
     to be split by shard first.
@@ -41,7 +43,8 @@ def sharded_topk_score(Xq: torch.Tensor, Y_local: torch.Tensor, K: int,
                                  ban_indptr=ban_indptr,
                                  ban_indices=ban_indices,
                                  item_cats=item_cats,
-                                 query_cats=query_cats)
+                                 query_cats=query_cats,
+                                 item_weights=item_weights)
     gidx = torch.where(idx >= 0, idx + item_base, idx)
     if not pdist.is_distributed():
         return v, gidx

@@ -16,7 +16,13 @@ ECommAlgorithm.scala (649 LoC):
     (:541-599): cosine vs recent view items; if none → predictDefault
     (:508-539): popularity ranking
   * optional weightedItems score multipliers (:400-430, adjust-score
-    variant)
+    variant): the latest `$set constraint weightedItems` (property
+    `weights`), else the `weightedItems` engine parameter. The served
+    score is score * weight and the top num is taken on THAT product,
+    inside the fused kernels (topk_score's item_weights), as the
+    reference's adjustedScore-then-getTopN does. Unlike the reference
+    this template does not drop scores <= 0, so a weight of 0 is not a
+    filter: hide items with blackList / unavailableItems.
 
 MI355X design: all three scoring paths are fused masked top-K kernel
 launches over device-resident factors.
@@ -195,6 +201,27 @@ class ECommModel:
         self.category_bits = category_bits
         self._cat_bits_built = (category_bits_built
                                 or category_bits is not None)
+        self._weights_key = None
+        self._weights = None
+
+    def item_weights(self, groups) -> Optional[torch.Tensor]:
+        """The [N] fp32 weight vector of `groups` ([WeightGroup]) on the
+        factors' device; an item in several groups takes the product of
+        their weights. Cached on the model, keyed by the groups, so it is
+        not rebuilt per query. None when there are no groups."""
+        if not groups:
+            return None
+        key = tuple((frozenset(g.items), g.weight) for g in groups)
+        if getattr(self, "_weights_key", None) != key:
+            w = torch.ones(len(self.item_map), dtype=torch.float32)
+            for g in groups:
+                rows = [self.item_map[x] for x in g.items
+                        if x in self.item_map]
+                if rows:
+                    w[torch.tensor(rows)] *= g.weight
+            self._weights = w.to(self.item_factors.device)
+            self._weights_key = key
+        return self._weights
 
     def cat_bits(self):
         """Category bit words for the fused per-query filter (train-time;
@@ -369,25 +396,22 @@ class ECommAlgorithm(Algorithm):
         return mask
 
     def _weight_groups(self) -> List[WeightGroup]:
-        """adjust-score variant: [{"items": [...], "weight": w}]
+        """adjust-score variant: [{"items": [...], "weight": w}] from the
+        latest `$set constraint weightedItems` (property `weights`; one
+        live lookup, 200 ms), else the weightedItems engine parameter
         (weightedItems :400-430)."""
+        raw = self.params.get("weightedItems", [])
+        try:
+            constr = event_store.find_by_entity(
+                app_name=self.params["appName"], entity_type="constraint",
+                entity_id="weightedItems", event_names=["$set"],
+                limit=1, latest=True, timeout=0.2)
+            if constr:
+                raw = constr[0].properties.get("weights") or []
+        except TimeoutError:
+            pass
         return [WeightGroup(set(g["items"]), float(g["weight"]))
-                for g in self.params.get("weightedItems", [])]
-
-    def _apply_weights(self, model, scores: List[ItemScore]
-                       ) -> List[ItemScore]:
-        groups = self._weight_groups()
-        if not groups:
-            return scores
-        out = []
-        for s in scores:
-            w = 1.0
-            for g in groups:
-                if s.item in g.items:
-                    w *= g.weight
-            out.append(ItemScore(s.item, s.score * w))
-        out.sort(key=lambda s: -s.score)
-        return out
+                for g in raw]
 
     # ------------------------------------------------------------ predict
 
@@ -401,9 +425,10 @@ class ECommAlgorithm(Algorithm):
                        if x in model.item_map})
 
     def _topk(self, model, Xq, mask, num, cands=None,
-              Y=None) -> List[ItemScore]:
+              Y=None, weights=None) -> List[ItemScore]:
         """One query's top-K over Y (item_factors by default). With
-        `cands` (a sorted list of item rows) only those rows are read."""
+        `cands` (a sorted list of item rows) only those rows are read;
+        `weights` is the [N] score-weight vector or None."""
         from predictionio_amd.templates.common import ban_csr
         Y = model.item_factors if Y is None else Y
         kw = {}
@@ -411,15 +436,16 @@ class ECommAlgorithm(Algorithm):
             kw["cand_indptr"], kw["cand_indices"] = ban_csr([cands],
                                                             Y.device)
         v, idx = topk_ops.topk_score(Xq.contiguous(), Y, num,
-                                     item_mask=mask, **kw)
+                                     item_mask=mask, item_weights=weights,
+                                     **kw)
         v, idx = v[0].cpu(), idx[0].cpu()
         return [ItemScore(model.item_inv[int(i)], float(s))
                 for s, i in zip(v, idx) if i >= 0]
 
-    def _topk_cos(self, model, Xq, mask, num, cands=None
+    def _topk_cos(self, model, Xq, mask, num, cands=None, weights=None
                   ) -> List[ItemScore]:
         return self._topk(model, Xq, mask, num, cands,
-                          model.item_factors_norm)
+                          model.item_factors_norm, weights)
 
     def _recent_items(self, q: Query) -> List[str]:
         """Latest N similarEvents of the user (getRecentItems :430-467)."""
@@ -440,10 +466,11 @@ class ECommAlgorithm(Algorithm):
         # a whiteList is the kernel's candidate list, not an N-byte mask
         cands = self._cands(model, q)
         mask = self._mask(model, q, black, white=False)
+        weights = model.item_weights(self._weight_groups())
         uidx = model.user_map.get(q.user)
         if uidx is not None and uidx < model.user_features.shape[0]:
             scores = self._topk(model, model.user_features[uidx:uidx + 1],
-                                mask, q.num, cands)
+                                mask, q.num, cands, weights=weights)
         else:
             recent = [model.item_map[i] for i in self._recent_items(q)
                       if i in model.item_map]
@@ -452,11 +479,12 @@ class ECommAlgorithm(Algorithm):
                 Xq = model.item_factors_norm[
                     torch.tensor(recent, device=dev)].sum(dim=0,
                                                           keepdim=True)
-                scores = self._topk_cos(model, Xq, mask, q.num, cands)
+                scores = self._topk_cos(model, Xq, mask, q.num, cands,
+                                        weights)
             else:
                 scores = self._predict_default(
-                    model, self._mask(model, q, black), q)
-        return PredictedResult(self._apply_weights(model, scores)[:q.num])
+                    model, self._mask(model, q, black), q, weights)
+        return PredictedResult(scores[:q.num])
 
     def batch_predict(self, model: ECommModel, queries):
         """Device-batched predict: at most two fused top-K launches for
@@ -466,7 +494,8 @@ class ECommAlgorithm(Algorithm):
         `categories` becomes a row of category bit words, blackList +
         seen items a sorted ban list in one CSR and a whiteList a row of
         the candidate CSR; the unavailableItems constraint is fetched
-        once per batch and becomes the shared item_mask. Live per-user
+        once per batch and becomes the shared item_mask, and so are the
+        weight groups, whose [N] vector goes to every launch. Live per-user
         lookups stay per query. Models without category bits go through
         predict() one by one."""
         qs = [(i, q if isinstance(q, Query) else Query.from_json(q))
@@ -480,6 +509,7 @@ class ECommAlgorithm(Algorithm):
             dev = model.item_factors.device
             n = len(model.item_map)
             unavailable = self._unavailable_items()
+            weights = model.item_weights(self._weight_groups())
             item_mask = None
             un_idx = [model.item_map[x] for x in unavailable
                       if x in model.item_map]
@@ -500,10 +530,9 @@ class ECommAlgorithm(Algorithm):
                 if recent:
                     cold.append((i, q, ban, recent))
                 else:
-                    out[i] = PredictedResult(self._apply_weights(
-                        model, self._predict_default(
-                            model, self._mask(model, q, black | unavailable),
-                            q))[:q.num])
+                    out[i] = PredictedResult(self._predict_default(
+                        model, self._mask(model, q, black | unavailable),
+                        q, weights)[:q.num])
             # each group: its plain queries, then its whiteList queries
             for white in (False, True):
                 sub = [g for g in known
@@ -513,7 +542,7 @@ class ECommAlgorithm(Algorithm):
                         torch.tensor([g[3] for g in sub], device=dev)]
                     self._batch_topk(model, bits, sub, Xq,
                                      model.item_factors, item_mask, out,
-                                     white)
+                                     white, weights)
                 sub = [g for g in cold
                        if (g[1].white_list is not None) == white]
                 if sub:
@@ -527,11 +556,11 @@ class ECommAlgorithm(Algorithm):
                                      dtype=Yn.dtype, device=dev
                                      ).index_add_(0, seg, Yn[rows])
                     self._batch_topk(model, bits, sub, Xq, Yn, item_mask,
-                                     out, white)
+                                     out, white, weights)
         return [(i, out[i]) for i, _ in qs]
 
     def _batch_topk(self, model, bits, group, Xq, Y, item_mask, out,
-                    white=False):
+                    white=False, weights=None):
         """One fused launch for `group` [(i, q, ban list, _)]; K is the
         group's largest num and every result is cut to its own. white:
         every query of the group has a whiteList, which becomes its row
@@ -550,7 +579,7 @@ class ECommAlgorithm(Algorithm):
         v, ix = topk_ops.topk_score(
             Xq, Y, num, item_mask=item_mask, ban_indptr=ban_indptr,
             ban_indices=ban_indices, item_cats=bits.item_words,
-            query_cats=query_cats, **kw)
+            query_cats=query_cats, item_weights=weights, **kw)
         v_np = v.cpu().numpy()
         ix_np = ix.cpu().numpy()
         names = model.item_inv_np()[np.clip(ix_np, 0, None)]
@@ -559,15 +588,17 @@ class ECommAlgorithm(Algorithm):
             scores = [ItemScore(nm, float(s)) for nm, s, it in
                       zip(names[r, :q.num], v_np[r, :q.num],
                           ix_np[r, :q.num]) if it >= 0]
-            out[i] = PredictedResult(
-                self._apply_weights(model, scores)[:q.num])
+            out[i] = PredictedResult(scores)
 
-    def _predict_default(self, model: ECommModel, mask, q: Query
-                         ) -> List[ItemScore]:
-        """Popularity ranking under the same filters (:508-539)."""
+    def _predict_default(self, model: ECommModel, mask, q: Query,
+                         weights=None) -> List[ItemScore]:
+        """Popularity ranking under the same filters (:508-539): buy
+        counts times the item weights, then the top num."""
         m = mask.cpu()
+        w = weights.cpu() if weights is not None else None
         ranked = sorted(
-            ((c, i) for i, c in model.popular_count.items()
+            ((c * float(w[i]) if w is not None else c, i)
+             for i, c in model.popular_count.items()
              if not bool(m[i])), reverse=True)[:q.num]
         return [ItemScore(model.item_inv[i], float(c)) for c, i in ranked]
 
