@@ -83,6 +83,9 @@ class ALSTrainer:
         self.i_lo, self.i_hi = pdist.block_bounds(n_items, world, rank)
         self.user_csr = None   # (indptr, indices, values) local users x items
         self.item_csr = None   # (indptr, indices, values) local items x users
+        # heavy-row plans of the two CSRs (ops.als.HeavyPlan), GPU only
+        self._user_plan = None
+        self._item_plan = None
         self.X: Optional[torch.Tensor] = None  # local user factors
         self.Y: Optional[torch.Tensor] = None  # local item factors
         self._pending_y = None  # in-flight Y gather from the item half
@@ -109,6 +112,15 @@ class ALSTrainer:
         self.item_csr = als_ops.build_csr(
             items[i_mask] - self.i_lo, users[i_mask], ratings[i_mask],
             self.i_hi - self.i_lo)
+        self._plan_heavy_rows()
+
+    def _plan_heavy_rows(self) -> None:
+        """One heavy-row plan per CSR, made once here; every half-step
+        narrows it to its row chunks on the host."""
+        self._user_plan = self._item_plan = None
+        if self.user_csr[0].is_cuda:
+            self._user_plan = als_ops.heavy_plan(self.user_csr[0])
+            self._item_plan = als_ops.heavy_plan(self.item_csr[0])
 
     def set_ratings_sharded(self, user_shard, item_shard) -> None:
         """Directly install pre-sharded triples: user_shard = (u, i, r) for
@@ -122,6 +134,7 @@ class ALSTrainer:
         self.item_csr = als_ops.build_csr(
             i2.to(self.device), u2.to(self.device), r2.to(self.device),
             self.i_hi - self.i_lo)
+        self._plan_heavy_rows()
 
     def init_factors(self) -> None:
         """Random init, matching MLlib's scheme (unit-scaled gaussian /
@@ -143,7 +156,7 @@ class ALSTrainer:
         return time.time()
 
     def _solve_half(self, csr, fixed_full: torch.Tensor,
-                    yty, n_local: int, n_out_total: int):
+                    yty, n_local: int, n_out_total: int, plan=None):
         """Chunked fused solve into a zero-padded [max_rows, f] block;
         each chunk's output all-gather is issued asynchronously right
         after the chunk's kernels, so the collective for the NEXT
@@ -172,7 +185,7 @@ class ALSTrainer:
                     lam=self.p.lambda_, alpha=self.p.alpha,
                     implicit=self.p.implicit,
                     wr_scale=not self.p.implicit, lv=lv,
-                    row_range=(rl, rh), out=g.src[rl:rh])
+                    row_range=(rl, rh), out=g.src[rl:rh], plan=plan)
             g.push(c0, c1)
         return g.src[:n_local], g
 
@@ -208,7 +221,8 @@ class ALSTrainer:
             yty_w.wait()
         t1 = self._tsync() if timing else 0.0
         self.X, gx = self._solve_half(
-            self.user_csr, Yfull, yty, self.u_hi - self.u_lo, self.n_users)
+            self.user_csr, Yfull, yty, self.u_hi - self.u_lo, self.n_users,
+            self._user_plan)
         t2 = self._tsync() if timing else 0.0
         yty2 = yty2_w = None
         if implicit:
@@ -221,7 +235,8 @@ class ALSTrainer:
             yty2_w.wait()
         t3 = self._tsync() if timing else 0.0
         self.Y, self._pending_y = self._solve_half(
-            self.item_csr, Xfull, yty2, self.i_hi - self.i_lo, self.n_items)
+            self.item_csr, Xfull, yty2, self.i_hi - self.i_lo, self.n_items,
+            self._item_plan)
         if timing:
             t4 = self._tsync()
             self.phase_times["gather_s"] += (t1 - t0) + (t3 - t2)

@@ -7,7 +7,8 @@ is the numerics reference the GPU kernel is validated against.
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import os
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -75,6 +76,141 @@ def woodbury_lv(Y: torch.Tensor, YtY: torch.Tensor,
     return Linv, V
 
 
+# ------------------------------------------------------------ heavy rows
+#
+# Rows of degree > heavy_min() leave the one-unit-per-row solvers for the
+# split-row route (csrc/als_heavy.hip): chunks of heavy_chunk() consecutive
+# CSR entries, one workgroup each. Both defaults are measured
+# (scripts/als_heavy_probe.py, table in NOTES.md).
+
+HEAVY_MIN_DEFAULT = 4096
+HEAVY_CHUNK_DEFAULT = 8192
+_HEAVY_FLOOR = 64      # the Woodbury kernels own rows up to degree 48
+_INT_MAX = 2 ** 31 - 1
+
+_heavy_stats: Dict[str, int] = {"calls": 0, "rows": 0, "chunks": 0}
+
+
+def heavy_stats() -> Dict[str, int]:
+    """Cumulative counters of the split-row route since import: solves that
+    took it, heavy rows solved and chunks launched."""
+    return dict(_heavy_stats)
+
+
+def heavy_min() -> int:
+    """Rows of degree > this are heavy (PIO_ALS_HEAVY_MIN, read on every
+    call). 0 disables the route; other values below 64 count as 64, so a
+    heavy row is never a Woodbury row."""
+    v = int(os.environ.get("PIO_ALS_HEAVY_MIN", HEAVY_MIN_DEFAULT))
+    if v <= 0:
+        return 0
+    return min(max(v, _HEAVY_FLOOR), _INT_MAX)
+
+
+def heavy_chunk() -> int:
+    """CSR entries per chunk of a heavy row (PIO_ALS_HEAVY_CHUNK, read on
+    every call): a positive multiple of 32."""
+    v = int(os.environ.get("PIO_ALS_HEAVY_CHUNK", HEAVY_CHUNK_DEFAULT))
+    if v <= 0 or v % 32 or v > 1 << 24:
+        raise ValueError(
+            f"PIO_ALS_HEAVY_CHUNK = {v}: need a multiple of 32 in (0, 2^24]")
+    return v
+
+
+def _heavy_ws_bytes() -> int:
+    """Cap on the partial workspace: PIO_ALS_HEAVY_WS_MB MiB, default 256."""
+    return int(float(os.environ.get("PIO_ALS_HEAVY_WS_MB", "256")) * 2 ** 20)
+
+
+class HeavyPlan:
+    """The heavy rows of one CSR and their chunk table, on the host:
+    rows [H] (ascending row ids), chunk_ptr [H + 1] and chunks [C, 2]
+    (entry start, end; absolute offsets into indices / values), all int64.
+    The chunk length is fixed, so a row's chunks depend on its own degree
+    only. Device copies are made once per (row range, device)."""
+
+    def __init__(self, rows, chunk_ptr, chunks, n_rows, hmin, chunk):
+        self.rows, self.chunk_ptr, self.chunks = rows, chunk_ptr, chunks
+        self.n_rows, self.heavy_min, self.chunk = n_rows, hmin, chunk
+        self._dev: dict = {}
+        self._narrowed: dict = {}
+
+    @classmethod
+    def build(cls, indptr: torch.Tensor, hmin: Optional[int] = None,
+              chunk: Optional[int] = None) -> "HeavyPlan":
+        """From a row-pointer array on any device: one reduction and one
+        small transfer."""
+        hmin = heavy_min() if hmin is None else hmin
+        chunk = heavy_chunk() if chunk is None else chunk
+        n_rows = indptr.shape[0] - 1
+        empty = torch.zeros(0, dtype=torch.int64)
+        if hmin <= 0 or n_rows <= 0:
+            return cls(empty, torch.zeros(1, dtype=torch.int64),
+                       empty.view(0, 2), n_rows, hmin, chunk)
+        deg = indptr[1:] - indptr[:-1]
+        rows = torch.nonzero(deg > hmin).flatten()
+        se = torch.stack([rows, indptr[rows], indptr[rows + 1]]).cpu()
+        rows, start, end = se[0], se[1], se[2]
+        n_c = (end - start + chunk - 1) // chunk
+        chunk_ptr = torch.zeros(rows.numel() + 1, dtype=torch.int64)
+        torch.cumsum(n_c, 0, out=chunk_ptr[1:])
+        owner = torch.repeat_interleave(torch.arange(rows.numel()), n_c)
+        k = torch.arange(int(chunk_ptr[-1])) - chunk_ptr[owner]
+        c_lo = start[owner] + k * chunk
+        c_hi = torch.minimum(c_lo + chunk, end[owner])
+        return cls(rows.contiguous(), chunk_ptr,
+                   torch.stack([c_lo, c_hi], 1).contiguous(), n_rows, hmin,
+                   chunk)
+
+    def narrow(self, lo: int, hi: int) -> "HeavyPlan":
+        """The plan of rows [lo, hi), row ids rebased to lo (host only)."""
+        if (lo, hi) == (0, self.n_rows):
+            return self
+        got = self._narrowed.get((lo, hi))
+        if got is None:
+            a, b = torch.searchsorted(
+                self.rows, torch.tensor([lo, hi])).tolist()
+            cp = self.chunk_ptr[a:b + 1]
+            got = HeavyPlan((self.rows[a:b] - lo).contiguous(), cp - cp[0],
+                            self.chunks[int(cp[0]):int(cp[-1])].contiguous(),
+                            hi - lo, self.heavy_min, self.chunk)
+            self._narrowed[(lo, hi)] = got
+        return got
+
+    def on(self, device) -> tuple:
+        """(rows, chunk_ptr, chunks) on `device`."""
+        got = self._dev.get(device)
+        if got is None:
+            got = tuple(t.to(device) for t in
+                        (self.rows, self.chunk_ptr, self.chunks))
+            self._dev[device] = got
+        return got
+
+
+def heavy_plan(indptr: torch.Tensor) -> HeavyPlan:
+    """The HeavyPlan of a whole CSR under the knobs in force: build it once
+    per CSR and hand it to every als_solve over that CSR."""
+    return HeavyPlan.build(indptr)
+
+
+def _heavy_pass(ext, hp: HeavyPlan, ix, vv, Yp, YtYp, X, lam, alpha,
+                implicit, wr_scale) -> None:
+    """Solve hp's rows into X (rows of hp index X) on the split-row route."""
+    # the kernels trust the tables: check them where that costs nothing
+    if (int(hp.rows[-1]) >= X.shape[0] or int(hp.rows[0]) < 0
+            or int(hp.chunks.min()) < 0
+            or int(hp.chunks.max()) > ix.numel()
+            or bool((hp.chunks[:, 1] <= hp.chunks[:, 0]).any())):
+        raise ValueError("heavy-row plan does not fit this CSR")
+    rows, chunk_ptr, chunks = hp.on(X.device)
+    ext.als_heavy_solve(ix, vv, Yp, YtYp, X, rows, chunk_ptr, chunks,
+                        hp.chunk_ptr, float(lam), float(alpha),
+                        bool(implicit), bool(wr_scale), _heavy_ws_bytes())
+    _heavy_stats["calls"] += 1
+    _heavy_stats["rows"] += hp.rows.numel()
+    _heavy_stats["chunks"] += hp.chunks.shape[0]
+
+
 def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
               values: torch.Tensor, Y: torch.Tensor,
               YtY: Optional[torch.Tensor] = None,
@@ -82,7 +218,8 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
               implicit: bool = False, wr_scale: bool = True,
               lv: Optional[tuple] = None,
               row_range: Optional[Tuple[int, int]] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None,
+              plan: Optional[HeavyPlan] = None) -> torch.Tensor:
     """Solve all rows of one ALS half-iteration.
 
     explicit: (sum y y^T + lam*nnz*I) x = sum r*y      (ALS-WR, like MLlib)
@@ -93,15 +230,20 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
     linear system through the push-through identity). Implicit mode runs
     three phases: the Woodbury kernel emits whitened Z rows, one
     row-transform launch maps Z -> X = Z L^-1 for all rows, then the dense kernel fills
-    the big (nnz > 32) rows directly.
+    the big (nnz > 32) rows directly. Rows of degree > heavy_min() are
+    skipped by all of these and solved last by the split-row route
+    (HeavyPlan, csrc/als_heavy.hip), which writes X directly.
 
     lv: optional precomputed (Linv, V) from prepare_lv() — hoist it when
     solving in row chunks (the multi-GPU gather/solve overlap path).
     row_range: solve only rows [lo, hi) of the CSR (indices/values stay
     whole; indptr offsets are absolute). out: optional [rows, f] target
     written in place (enables chunked solves into one padded buffer).
+    plan: optional heavy_plan(indptr) of the whole CSR; without it (or if
+    the knobs changed since it was made) the call builds its own.
     """
     check_row_count(indptr=indptr.shape[0] - 1, Y=Y.shape[0])
+    n_all = indptr.shape[0] - 1
     if implicit:
         wr_scale = False  # Hu-Koren regularizes with plain lambda*I
         if YtY is None:
@@ -132,6 +274,20 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
                 raise ValueError(
                     f"CSR column id out of range: [{int(ix.min())}, {mx}]"
                     f" vs {Y.shape[0]} factor rows")
+        # heavy rows: the dense kernels skip them, the split-row pass at
+        # the end solves them
+        hp = None
+        hmin = heavy_min()
+        if hmin > 0 and ix.numel() > hmin:
+            chunk = heavy_chunk()
+            if (plan is not None and plan.n_rows == n_all
+                    and (plan.heavy_min, plan.chunk) == (hmin, chunk)):
+                hp = plan.narrow(*row_range) if row_range else plan
+            else:
+                hp = HeavyPlan.build(ip, hmin, chunk)
+            if hp.rows.numel() == 0:
+                hp = None
+        above = hmin if hp is not None else _INT_MAX
         direct_out = (out if out is not None and pf == f
                       and out.is_contiguous() else None)
         if implicit and pf <= 128:
@@ -147,16 +303,20 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
                     and V.dtype == torch.float32:
                 V = V.to(torch.bfloat16).contiguous()
             Z = ext.als_solve(ip, ix, vv, Yp, YtYp, V, float(lam),
-                              float(alpha), True, False, 1, None)
+                              float(alpha), True, False, 1, None, None,
+                              above)
             # X = Z L^-1 for all rows (Woodbury rows hold z; big rows get
             # overwritten by the dense pass next)
             X = row_transform(Z, Linv, out=direct_out)
             ext.als_solve(ip, ix, vv, Yp, YtYp, None, float(lam),
-                          float(alpha), True, False, 2, X)
+                          float(alpha), True, False, 2, X, None, above)
         else:
             X = ext.als_solve(ip, ix, vv, Yp, YtYp, None, float(lam),
                               float(alpha), bool(implicit), bool(wr_scale),
-                              0, direct_out)
+                              0, direct_out, None, above)
+        if hp is not None:
+            _heavy_pass(ext, hp, ix, vv, Yp, YtYp, X, lam, alpha, implicit,
+                        wr_scale)
         res = X[:, :f].contiguous() if pf != f else X
         if out is not None and res.data_ptr() != out.data_ptr():
             out.copy_(res)

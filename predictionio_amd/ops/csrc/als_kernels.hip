@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
     float alpha,
     int implicit_mode,                      // 1 = Hu-Koren implicit
     int wr_scale,                           // 1 = scale lambda by nnz (ALS-WR)
-    int skip_below)                         // skip rows with nnz <= this
+    int skip_below,                         // skip rows with nnz <= this
+    int skip_above)                         // and rows with nnz > this
 {
   constexpr int TM = 4;                       // thread tile edge
   constexpr int TILES = (F / TM) * (F / TM);  // tiles covering FxF
@@ -120,7 +121,8 @@ __global__ __launch_bounds__(256) void als_solve_kernel(
     const long long start = indptr[row];
     const long long end = indptr[row + 1];
     const int nnz = (int)(end - start);
-    if (nnz <= skip_below) continue;  // Woodbury kernel owns these rows
+    // Woodbury kernel below, split-row solver (als_heavy.hip) above
+    if (nnz <= skip_below || nnz > skip_above) continue;
 
     // register accumulators: TPT tiles of TMxTM
     float acc[TPT][TM][TM];
@@ -1531,7 +1533,7 @@ extern "C" void launch_als_solve(
     const float* Y, const float* YtY, const float* V, float* X,
     int n_rows, int f, float lambda, float alpha,
     int implicit_mode, int wr_scale, int which,
-    unsigned long long* prof, hipStream_t stream)
+    unsigned long long* prof, int heavy_min, hipStream_t stream)
 {
   // >> 256 workgroups to fill 256 CUs across 8 XCDs; grid-stride for huge
   // row counts.
@@ -1554,7 +1556,11 @@ extern "C" void launch_als_solve(
   // side at 8 GPUs where nnz ~ 200). 0/unset = wave kernel takes all.
   const char* e_split = getenv("PIO_ALS_DENSE_SPLIT");
   const int dense_split = e_split ? atoi(e_split) : 0;
-  const int wave_hi = dense_split > 0 ? dense_split : 0x7fffffff;
+  // heavy_min: rows with nnz > heavy_min belong to the split-row solver
+  // (als_heavy.hip) and no kernel here touches them; INT_MAX when the
+  // call has no such row. The PIO_ALS_DENSE_SPLIT seam stays below it.
+  const int wave_hi =
+      dense_split > 0 && dense_split < heavy_min ? dense_split : heavy_min;
 #define LAUNCH_WAVE(FF)                                                      \
   if (dense && use_bf16s_g && FF == 64) {                                    \
   launch_wave_bf16g<FF>(grid_w, stream, indptr, indices, values, Y, YtY, X, \
@@ -1563,7 +1569,8 @@ extern "C" void launch_als_solve(
   if (dense_split > 0)                                                       \
     hipLaunchKernelGGL((als_solve_kernel<FF>), dim3(grid_b), dim3(256), 0,   \
                        stream, indptr, indices, values, Y, YtY, X, n_rows,   \
-                       lambda, alpha, implicit_mode, wr_scale, dense_split); \
+                       lambda, alpha, implicit_mode, wr_scale, dense_split,  \
+                       heavy_min);                                           \
   } else if (dense) {                                                        \
   hipLaunchKernelGGL((als_solve_wave_kernel<FF>), dim3(grid_w), dim3(128),   \
                      0, stream, indptr, indices, values, Y, YtY, X, n_rows,  \
@@ -1571,13 +1578,14 @@ extern "C" void launch_als_solve(
   if (dense_split > 0)                                                       \
     hipLaunchKernelGGL((als_solve_kernel<FF>), dim3(grid_b), dim3(256), 0,   \
                        stream, indptr, indices, values, Y, YtY, X, n_rows,   \
-                       lambda, alpha, implicit_mode, wr_scale, dense_split); \
+                       lambda, alpha, implicit_mode, wr_scale, dense_split,  \
+                       heavy_min);                                           \
   }
 #define LAUNCH_BLOCK(FF)                                                     \
   if (dense)                                                                 \
   hipLaunchKernelGGL((als_solve_kernel<FF>), dim3(grid_b), dim3(256), 0,     \
                      stream, indptr, indices, values, Y, YtY, X, n_rows,     \
-                     lambda, alpha, implicit_mode, wr_scale, skip)
+                     lambda, alpha, implicit_mode, wr_scale, skip, heavy_min)
   // PIO_ALS_DUAL=1 routes the Woodbury rows through the dual-row kernel
   // (two rows per wave) — A/B lever for the round-2 M-solve rework
   const char* e_dual = getenv("PIO_ALS_DUAL");

@@ -5,6 +5,8 @@
 
 #include <torch/extension.h>
 
+#include <climits>
+
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -15,7 +17,17 @@ extern "C" void launch_als_solve(
     const float* Y, const float* YtY, const float* V, float* X,
     int n_rows, int f, float lambda, float alpha,
     int implicit_mode, int wr_scale, int which,
-    unsigned long long* prof, hipStream_t stream);
+    unsigned long long* prof, int heavy_min, hipStream_t stream);
+
+extern "C" long long als_heavy_slot_floats(int f);
+
+extern "C" void launch_als_heavy(
+    const long long* chunks, const long long* chunk_ptr,
+    const long long* rows, const long long* chunk_ptr_host, int n_heavy,
+    const int* indices, const float* values, const float* Y,
+    const float* YtY, float* X, float* ws, long long ws_slots, float* carry,
+    int f, float lambda, float alpha, int implicit_mode, int wr_scale,
+    hipStream_t stream);
 
 extern "C" void launch_als_row_transform(
     const float* in, const float* W, float* out, long long n_rows, int f,
@@ -212,7 +224,8 @@ const float* check_item_weights(const c10::optional<torch::Tensor>& w,
 // V = Y L^-T (L = chol(YtY + lambda I)) precomputed on the host per
 // half-iteration enables the per-row Woodbury fast path in implicit mode
 // (see als_woodbury_kernel). which: 0 = both passes, 1 = Woodbury rows
-// only (emits Z), 2 = dense rows only (writes into `out`).
+// only (emits Z), 2 = dense rows only (writes into `out`). Rows of degree
+// > heavy_min are left to als_heavy_solve (INT_MAX: there are none).
 torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
                         torch::Tensor values, torch::Tensor Y,
                         c10::optional<torch::Tensor> YtY,
@@ -220,7 +233,10 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
                         double lambda, double alpha,
                         bool implicit_mode, bool wr_scale,
                         int64_t which, c10::optional<torch::Tensor> out,
-                        c10::optional<torch::Tensor> prof) {
+                        c10::optional<torch::Tensor> prof,
+                        int64_t heavy_min) {
+  TORCH_CHECK(heavy_min > 0 && heavy_min <= INT_MAX,
+              "heavy_min must be in [1, INT_MAX]");
   TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt64 &&
                   indptr.is_contiguous(), "indptr must be contiguous i64 GPU");
   TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
@@ -278,9 +294,83 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
                    values.data_ptr<float>(), Y.data_ptr<float>(), yty_ptr,
                    v_ptr, X.data_ptr<float>(), (int)n_rows, (int)f, (float)lambda,
                    (float)alpha, implicit_mode ? 1 : 0, wr_scale ? 1 : 0,
-                   (int)which, prof_ptr, stream);
+                   (int)which, prof_ptr, (int)heavy_min, stream);
   C10_HIP_CHECK(hipGetLastError());
   return X;
+}
+
+// The split-row pass for heavy rows (als_heavy.hip): per chunk of
+// consecutive CSR entries a partial normal matrix and right-hand side on
+// fp32 MFMA, then one solve per row over its partials in chunk order.
+// rows [H], chunk_ptr [H + 1] and chunks [C, 2] (entry start, end) are
+// i64 GPU tensors; chunk_ptr_host is chunk_ptr on the CPU. The caller has
+// checked them against X and the CSR. The partial workspace takes at most
+// ws_bytes; longer chunk tables are walked in batches.
+void als_heavy_solve(torch::Tensor indices, torch::Tensor values,
+                     torch::Tensor Y, c10::optional<torch::Tensor> YtY,
+                     torch::Tensor X, torch::Tensor rows,
+                     torch::Tensor chunk_ptr, torch::Tensor chunks,
+                     torch::Tensor chunk_ptr_host, double lambda,
+                     double alpha, bool implicit_mode, bool wr_scale,
+                     int64_t ws_bytes) {
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+                  indices.is_contiguous(), "indices must be contiguous i32 GPU");
+  check_cuda_f32(values, "values");
+  check_cuda_f32(Y, "Y");
+  check_cuda_f32(X, "X");
+  const int64_t f = Y.size(1);
+  TORCH_CHECK(supported_rank(f), "rank must be one of 16/32/64/128, got ", f);
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == f, "X must be n_rows x f");
+  TORCH_CHECK(indices.size(0) == values.size(0), "indices/values mismatch");
+  // factor rows are gathered in 16-byte quads
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Y.data_ptr()) % 16 == 0,
+              "Y must be 16-byte aligned");
+  const float* yty_ptr = nullptr;
+  if (YtY.has_value()) {
+    check_cuda_f32(*YtY, "YtY");
+    TORCH_CHECK(YtY->size(0) == f && YtY->size(1) == f, "YtY must be f x f");
+    yty_ptr = YtY->data_ptr<float>();
+  }
+  auto i64_gpu = [&](const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                    t.scalar_type() == torch::kInt64 &&
+                    t.device() == Y.device(),
+                name, " must be a contiguous i64 tensor on Y's device");
+  };
+  i64_gpu(rows, "rows");
+  i64_gpu(chunk_ptr, "chunk_ptr");
+  i64_gpu(chunks, "chunks");
+  const int64_t H = rows.numel();
+  TORCH_CHECK(H < INT_MAX, "too many heavy rows");
+  TORCH_CHECK(!chunk_ptr_host.is_cuda() && chunk_ptr_host.is_contiguous() &&
+                  chunk_ptr_host.scalar_type() == torch::kInt64 &&
+                  chunk_ptr_host.numel() == H + 1 && chunk_ptr.numel() == H + 1,
+              "chunk_ptr / chunk_ptr_host must hold rows + 1 i64 entries");
+  if (H == 0) return;
+  const int64_t* cp = chunk_ptr_host.data_ptr<int64_t>();
+  TORCH_CHECK(cp[0] == 0, "chunk_ptr must start at 0");
+  for (int64_t h = 0; h < H; ++h)
+    TORCH_CHECK(cp[h + 1] > cp[h], "every heavy row needs a chunk");
+  const int64_t C = cp[H];
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(0) == C && chunks.size(1) == 2,
+              "chunks must be [chunk_ptr[-1], 2]");
+  const int64_t slot = als_heavy_slot_floats((int)f);
+  int64_t slots = ws_bytes / (slot * (int64_t)sizeof(float));
+  slots = slots < 1 ? 1 : (slots > C ? C : slots);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  torch::Tensor ws = torch::empty({slots * slot}, Y.options());
+  torch::Tensor carry = torch::empty({2 * slot}, Y.options());
+  launch_als_heavy(
+      reinterpret_cast<const long long*>(chunks.data_ptr<int64_t>()),
+      reinterpret_cast<const long long*>(chunk_ptr.data_ptr<int64_t>()),
+      reinterpret_cast<const long long*>(rows.data_ptr<int64_t>()),
+      reinterpret_cast<const long long*>(cp), (int)H,
+      indices.data_ptr<int>(), values.data_ptr<float>(), Y.data_ptr<float>(),
+      yty_ptr, X.data_ptr<float>(), ws.data_ptr<float>(), (long long)slots,
+      carry.data_ptr<float>(), (int)f, (float)lambda, (float)alpha,
+      implicit_mode ? 1 : 0, wr_scale ? 1 : 0, stream);
+  C10_HIP_CHECK(hipGetLastError());
 }
 
 // out[N, f] = in[N, f] . W[f, f] in exact fp32 on the matrix pipe (see
@@ -935,7 +1025,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lambda_") = 0.01,
         py::arg("alpha") = 1.0, py::arg("implicit_mode") = false,
         py::arg("wr_scale") = true, py::arg("which") = 0,
-        py::arg("out") = py::none(), py::arg("prof") = py::none());
+        py::arg("out") = py::none(), py::arg("prof") = py::none(),
+        py::arg("heavy_min") = (int64_t)INT_MAX);
+  m.def("als_heavy_solve", &als_heavy_solve,
+        "Split-row ALS solve of heavy rows: MFMA partial Gramians per chunk",
+        py::arg("indices"), py::arg("values"), py::arg("Y"),
+        py::arg("YtY"), py::arg("X"), py::arg("rows"), py::arg("chunk_ptr"),
+        py::arg("chunks"), py::arg("chunk_ptr_host"), py::arg("lambda_"),
+        py::arg("alpha"), py::arg("implicit_mode"), py::arg("wr_scale"),
+        py::arg("ws_bytes") = (int64_t)256 << 20);
   m.def("als_row_transform", &als_row_transform,
         "out[N, f] = in[N, f] . W[f, f], fp32 MFMA row transform",
         py::arg("in_"), py::arg("W"), py::arg("out") = py::none());
