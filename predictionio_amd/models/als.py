@@ -46,6 +46,9 @@ class ALSParams:
                                 # is crash-resume for 100M-scale runs)
     loss_every: int = 0         # >0: evaluate the training objective after
                                 # every N-th iteration (ALSTrainer.loss)
+    nonnegative: bool = False   # factors constrained to >= 0 (MLlib's
+                                # setNonnegative): every half-step is an
+                                # exact NNLS solve (ops/csrc/als_nnls.hip)
     tol: float = 0.0            # >0: stop once an evaluation improves on
                                 # the one before by <= tol * |previous|;
                                 # implies loss_every = 1 if that is 0
@@ -147,6 +150,8 @@ class ALSTrainer:
                   / (f ** 0.5)).to(self.device)
         self.Y = (torch.randn((self.i_hi - self.i_lo, f), generator=g)
                   / (f ** 0.5)).to(self.device)
+        if self.p.nonnegative:   # a feasible start, as MLlib takes
+            self.X, self.Y = self.X.abs(), self.Y.abs()
 
     # ------------------------------------------------------------ training
 
@@ -170,7 +175,8 @@ class ALSTrainer:
                     if pdist.get_world_size() > 1 else 1)
         indptr, indices, values = csr
         lv = None
-        if self.p.implicit and fixed_full.is_cuda:
+        if (self.p.implicit and fixed_full.is_cuda
+                and not self.p.nonnegative):   # NNLS has no Woodbury form
             lv = als_ops.prepare_lv(fixed_full, yty, self.p.lambda_)
         step_rows = (g.max_rows + n_chunks - 1) // n_chunks
         for c in range(n_chunks):
@@ -179,7 +185,15 @@ class ALSTrainer:
             if c0 >= c1:
                 break
             rl, rh = min(c0, n_local), min(c1, n_local)
-            if rh > rl:
+            if rh > rl and self.p.nonnegative:
+                als_ops.als_solve(
+                    indptr, indices, values, fixed_full, YtY=yty,
+                    lam=self.p.lambda_, alpha=self.p.alpha,
+                    implicit=self.p.implicit,
+                    wr_scale=not self.p.implicit,
+                    row_range=(rl, rh), out=g.src[rl:rh], plan=plan,
+                    nonnegative=True)
+            elif rh > rl:
                 als_ops.als_solve(
                     indptr, indices, values, fixed_full, YtY=yty,
                     lam=self.p.lambda_, alpha=self.p.alpha,

@@ -97,6 +97,15 @@ def heavy_stats() -> Dict[str, int]:
     return dict(_heavy_stats)
 
 
+_nnls_stats: Dict[str, int] = {"calls": 0, "rows": 0}
+
+
+def nnls_stats() -> Dict[str, int]:
+    """Cumulative counters of the nonnegative solver since import: GPU
+    solves that took it (als_solve(nonnegative=True)) and rows solved."""
+    return dict(_nnls_stats)
+
+
 def heavy_min() -> int:
     """Rows of degree > this are heavy (PIO_ALS_HEAVY_MIN, read on every
     call). 0 disables the route; other values below 64 count as 64, so a
@@ -194,8 +203,9 @@ def heavy_plan(indptr: torch.Tensor) -> HeavyPlan:
 
 
 def _heavy_pass(ext, hp: HeavyPlan, ix, vv, Yp, YtYp, X, lam, alpha,
-                implicit, wr_scale) -> None:
-    """Solve hp's rows into X (rows of hp index X) on the split-row route."""
+                implicit, wr_scale, nonnegative=False, iters=None) -> None:
+    """Solve hp's rows into X (rows of hp index X) on the split-row route;
+    nonnegative: its partials go to the block-pivoting solver."""
     # the kernels trust the tables: check them where that costs nothing
     if (int(hp.rows[-1]) >= X.shape[0] or int(hp.rows[0]) < 0
             or int(hp.chunks.min()) < 0
@@ -203,9 +213,16 @@ def _heavy_pass(ext, hp: HeavyPlan, ix, vv, Yp, YtYp, X, lam, alpha,
             or bool((hp.chunks[:, 1] <= hp.chunks[:, 0]).any())):
         raise ValueError("heavy-row plan does not fit this CSR")
     rows, chunk_ptr, chunks = hp.on(X.device)
-    ext.als_heavy_solve(ix, vv, Yp, YtYp, X, rows, chunk_ptr, chunks,
-                        hp.chunk_ptr, float(lam), float(alpha),
-                        bool(implicit), bool(wr_scale), _heavy_ws_bytes())
+    if nonnegative:
+        ext.als_heavy_solve(ix, vv, Yp, YtYp, X, rows, chunk_ptr, chunks,
+                            hp.chunk_ptr, float(lam), float(alpha),
+                            bool(implicit), bool(wr_scale),
+                            _heavy_ws_bytes(), True, iters)
+    else:
+        ext.als_heavy_solve(ix, vv, Yp, YtYp, X, rows, chunk_ptr, chunks,
+                            hp.chunk_ptr, float(lam), float(alpha),
+                            bool(implicit), bool(wr_scale),
+                            _heavy_ws_bytes())
     _heavy_stats["calls"] += 1
     _heavy_stats["rows"] += hp.rows.numel()
     _heavy_stats["chunks"] += hp.chunks.shape[0]
@@ -219,7 +236,9 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
               lv: Optional[tuple] = None,
               row_range: Optional[Tuple[int, int]] = None,
               out: Optional[torch.Tensor] = None,
-              plan: Optional[HeavyPlan] = None) -> torch.Tensor:
+              plan: Optional[HeavyPlan] = None,
+              nonnegative: bool = False,
+              nnls_iters: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Solve all rows of one ALS half-iteration.
 
     explicit: (sum y y^T + lam*nnz*I) x = sum r*y      (ALS-WR, like MLlib)
@@ -241,7 +260,19 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
     written in place (enables chunked solves into one padded buffer).
     plan: optional heavy_plan(indptr) of the whole CSR; without it (or if
     the knobs changed since it was made) the call builds its own.
+
+    nonnegative: per row, minimise 1/2 x^T A x - b^T x over x >= 0 with
+    the A and b above (MLlib's setNonnegative), exactly, by block principal
+    pivoting. On GPU every row that is not heavy takes the fused kernels of
+    csrc/als_nnls.hip and the heavy rows take the split-row route with the
+    same solver behind its Gramians; there is no Woodbury form, so lv is
+    ignored. On CPU: als_solve_nnls_ref. nnls_iters: optional int32 [rows]
+    GPU tensor that receives the solver's trip count per row (a probe's
+    output; needs nonnegative).
     """
+    if nnls_iters is not None and not (nonnegative and Y.is_cuda):
+        raise ValueError("nnls_iters is an output of the GPU nonnegative "
+                         "solver")
     check_row_count(indptr=indptr.shape[0] - 1, Y=Y.shape[0])
     n_all = indptr.shape[0] - 1
     if implicit:
@@ -290,7 +321,14 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
         above = hmin if hp is not None else _INT_MAX
         direct_out = (out if out is not None and pf == f
                       and out.is_contiguous() else None)
-        if implicit and pf <= 128:
+        if nonnegative:
+            X = ext.als_nnls_solve(ip, ix, vv, Yp, YtYp, float(lam),
+                                   float(alpha), bool(implicit),
+                                   bool(wr_scale), direct_out, above,
+                                   nnls_iters)
+            _nnls_stats["calls"] += 1
+            _nnls_stats["rows"] += ip.shape[0] - 1
+        elif implicit and pf <= 128:
             if lv is not None:
                 Linv, V = lv
             else:
@@ -315,15 +353,23 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
                               float(alpha), bool(implicit), bool(wr_scale),
                               0, direct_out, None, above)
         if hp is not None:
-            _heavy_pass(ext, hp, ix, vv, Yp, YtYp, X, lam, alpha, implicit,
-                        wr_scale)
+            if nonnegative:
+                _heavy_pass(ext, hp, ix, vv, Yp, YtYp, X, lam, alpha,
+                            implicit, wr_scale, True, nnls_iters)
+            else:
+                _heavy_pass(ext, hp, ix, vv, Yp, YtYp, X, lam, alpha,
+                            implicit, wr_scale)
         res = X[:, :f].contiguous() if pf != f else X
         if out is not None and res.data_ptr() != out.data_ptr():
             out.copy_(res)
             return out
         return res
-    res = als_solve_ref(indptr, indices, values, Y, YtY, lam, alpha,
-                        implicit, wr_scale)
+    if nonnegative:
+        res = als_solve_nnls_ref(indptr, indices, values, Y, YtY, lam,
+                                 alpha, implicit, wr_scale)
+    else:
+        res = als_solve_ref(indptr, indices, values, Y, YtY, lam, alpha,
+                            implicit, wr_scale)
     if out is not None:
         out.copy_(res)
         return out
@@ -374,6 +420,81 @@ def als_solve_ref(indptr, indices, values, Y, YtY=None, lam=0.01, alpha=1.0,
             A = Yr.t() @ Yr + lam * (nnz if wr_scale else 1.0) * eye
             b = Yr.t() @ v
         X[r] = torch.linalg.solve(A, b)
+    return X
+
+
+def normal_equations(indptr, indices, values, Y, YtY, lam, alpha, implicit,
+                     wr_scale, r):
+    """(A, b) of row r as in als_solve's docstring, in Y's dtype. An
+    explicit row without ratings gives A = 0, b = 0."""
+    f = Y.shape[1]
+    s, e = int(indptr[r]), int(indptr[r + 1])
+    Yr = Y[indices[s:e].long()]
+    v = values[s:e].to(Y.dtype)
+    eye = torch.eye(f, dtype=Y.dtype, device=Y.device)
+    if implicit:
+        A = ((YtY if YtY is not None else gramian(Y))
+             + (Yr.t() * (alpha * v)) @ Yr + lam * eye)
+        return A, Yr.t() @ (1.0 + alpha * v)
+    return (Yr.t() @ Yr + lam * ((e - s) if wr_scale else 1.0) * eye,
+            Yr.t() @ v)
+
+
+NNLS_REF_MAX_IT = 64  # the kernels' NNLS_MAX_IT
+
+
+def nnls_block_pivot(A: torch.Tensor, b: torch.Tensor,
+                     max_it: int = NNLS_REF_MAX_IT):
+    """argmin 1/2 x^T A x - b^T x over x >= 0 for symmetric positive
+    definite A by block principal pivoting with the backup exchange rule
+    (Kim and Park), in A's dtype: the algorithm of csrc/als_nnls.hip step
+    for step. Returns (x, trips)."""
+    f = A.shape[0]
+    eye = torch.eye(f, dtype=A.dtype, device=A.device)
+    P = torch.zeros(f, dtype=torch.bool, device=A.device)
+    x, y = torch.zeros_like(b), -b
+    p, ninf, it = 3, f + 1, 0
+    while it < max_it:
+        bad = torch.where(P, x < 0, y < 0)
+        nb = int(bad.sum())
+        if nb == 0:
+            break
+        if nb < ninf:
+            ninf, p = nb, 3
+        elif p > 0:
+            p -= 1
+        else:   # backup rule: the infeasible coordinate of largest index
+            k = int(torch.nonzero(bad).max())
+            bad = torch.zeros_like(bad)
+            bad[k] = True
+        P = P ^ bad
+        M = torch.where(P[:, None] & P[None, :], A, eye)
+        rhs = torch.where(P, b, torch.zeros_like(b))
+        x = torch.cholesky_solve(rhs[:, None],
+                                 torch.linalg.cholesky(M))[:, 0] * P
+        y = (A @ x - b) * ~P
+        it += 1
+    return x.clamp_min(0), it
+
+
+def als_solve_nnls_ref(indptr, indices, values, Y, YtY=None, lam=0.01,
+                       alpha=1.0, implicit=False,
+                       wr_scale=True) -> torch.Tensor:
+    """Pure-torch reference of als_solve(nonnegative=True): the normal
+    equations of als_solve_ref, then nnls_block_pivot, in Y's dtype (the
+    CPU path; the GPU tests run it in float64). Rows without ratings give
+    zeros in both modes (b = 0)."""
+    n_rows = indptr.shape[0] - 1
+    X = torch.zeros((n_rows, Y.shape[1]), dtype=Y.dtype, device=Y.device)
+    if implicit:
+        wr_scale = False
+        if YtY is None:
+            YtY = gramian(Y)
+    for r in range(n_rows):
+        if indptr[r + 1] > indptr[r]:
+            A, b = normal_equations(indptr, indices, values, Y, YtY, lam,
+                                    alpha, implicit, wr_scale, r)
+            X[r] = nnls_block_pivot(A, b)[0]
     return X
 
 

@@ -20,7 +20,7 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
            "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
            "cooc_topn.hip", "topk_cand.hip", "indicator_topk.hip",
            "rank_count.hip", "topk_kernels_wt.hip", "topk_mfma_wt.hip",
-           "als_heavy.hip"]
+           "als_heavy.hip", "als_nnls.hip"]
 # compiled on their own with packed fp32 VALU ops off (the vectorizer may
 # otherwise pair independent fp32 chains), then linked with the rest.
 # cooc_topn.hip is here since its LLR score stage: today it holds no
@@ -38,9 +38,11 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
 # the unweighted ones stay in their own files, built as before.
 # als_heavy.hip: the weight products that feed its MFMAs and its ordered
 # partial sums are independent fp32 chains the vectorizer could pair.
+# als_nnls.hip: the same Gramian tile loop, and the ordered fma chains of
+# its Cholesky, substitutions and gradient must not be re-associated.
 NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip", "indicator_topk.hip",
                   "rank_count.hip", "topk_kernels_wt.hip",
-                  "topk_mfma_wt.hip", "als_heavy.hip"]
+                  "topk_mfma_wt.hip", "als_heavy.hip", "als_nnls.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

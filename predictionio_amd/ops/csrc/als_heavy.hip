@@ -396,6 +396,29 @@ extern "C" long long als_heavy_slot_floats(int f) {
   return (long long)f * f + f;
 }
 
+// The Gramian launch alone, over n_chunks chunks into ws slots 0.. in
+// table order: for a solver of its own over the same partials (the
+// nonnegative one in als_nnls.hip).
+extern "C" void launch_als_heavy_gramian(
+    const long long* chunks, int n_chunks, const int* indices,
+    const float* values, const float* Y, float* ws, int f, float alpha,
+    int implicit_mode, hipStream_t stream)
+{
+  if (n_chunks <= 0) return;
+#define GRAMIAN(FF)                                                          \
+  hipLaunchKernelGGL((als_heavy_gramian_kernel<FF>), dim3(n_chunks),         \
+                     dim3(256), 0, stream, chunks, indices, values, Y, ws,   \
+                     alpha, implicit_mode)
+  switch (f) {
+    case 16: GRAMIAN(16); break;
+    case 32: GRAMIAN(32); break;
+    case 64: GRAMIAN(64); break;
+    case 128: GRAMIAN(128); break;
+    default: break;  // caller validates
+  }
+#undef GRAMIAN
+}
+
 // chunk_ptr_host is chunk_ptr on the host: n_heavy + 1 ascending entries
 // from 0, every row with at least one chunk. ws holds ws_slots >= 1 slots.
 extern "C" void launch_als_heavy(

@@ -29,6 +29,22 @@ extern "C" void launch_als_heavy(
     int f, float lambda, float alpha, int implicit_mode, int wr_scale,
     hipStream_t stream);
 
+extern "C" int als_nnls_max_it();
+
+extern "C" void launch_als_nnls(
+    const long long* indptr, const int* indices, const float* values,
+    const float* Y, const float* YtY, float* X, int* iters, int n_rows,
+    int f, float lambda, float alpha, int implicit_mode, int wr_scale,
+    int skip_above, hipStream_t stream);
+
+extern "C" void launch_als_heavy_nnls(
+    const long long* chunks, const long long* chunk_ptr,
+    const long long* rows, const long long* chunk_ptr_host, int n_heavy,
+    const int* indices, const float* values, const float* Y,
+    const float* YtY, float* X, int* iters, float* ws, long long ws_slots,
+    float* carry, int f, float lambda, float alpha, int implicit_mode,
+    int wr_scale, hipStream_t stream);
+
 extern "C" void launch_als_row_transform(
     const float* in, const float* W, float* out, long long n_rows, int f,
     int n_cu, hipStream_t stream);
@@ -306,13 +322,23 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
 // i64 GPU tensors; chunk_ptr_host is chunk_ptr on the CPU. The caller has
 // checked them against X and the CSR. The partial workspace takes at most
 // ws_bytes; longer chunk tables are walked in batches.
+// nonnegative: the partials go to the block-pivoting solver of
+// als_nnls.hip instead of the Cholesky solve; iters, if given, receives
+// that solver's trip count per row of X.
+int* check_iters(const c10::optional<torch::Tensor>& iters,
+                 const torch::Tensor& X);
+
 void als_heavy_solve(torch::Tensor indices, torch::Tensor values,
                      torch::Tensor Y, c10::optional<torch::Tensor> YtY,
                      torch::Tensor X, torch::Tensor rows,
                      torch::Tensor chunk_ptr, torch::Tensor chunks,
                      torch::Tensor chunk_ptr_host, double lambda,
                      double alpha, bool implicit_mode, bool wr_scale,
-                     int64_t ws_bytes) {
+                     int64_t ws_bytes, bool nonnegative,
+                     c10::optional<torch::Tensor> iters) {
+  TORCH_CHECK(nonnegative || !iters.has_value(),
+              "iters is an output of the nonnegative solver");
+  int* iters_ptr = check_iters(iters, X);
   TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
                   indices.is_contiguous(), "indices must be contiguous i32 GPU");
   check_cuda_f32(values, "values");
@@ -361,6 +387,18 @@ void als_heavy_solve(torch::Tensor indices, torch::Tensor values,
   hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   torch::Tensor ws = torch::empty({slots * slot}, Y.options());
   torch::Tensor carry = torch::empty({2 * slot}, Y.options());
+  if (nonnegative)
+    launch_als_heavy_nnls(
+        reinterpret_cast<const long long*>(chunks.data_ptr<int64_t>()),
+        reinterpret_cast<const long long*>(chunk_ptr.data_ptr<int64_t>()),
+        reinterpret_cast<const long long*>(rows.data_ptr<int64_t>()),
+        reinterpret_cast<const long long*>(cp), (int)H,
+        indices.data_ptr<int>(), values.data_ptr<float>(),
+        Y.data_ptr<float>(), yty_ptr, X.data_ptr<float>(), iters_ptr,
+        ws.data_ptr<float>(), (long long)slots, carry.data_ptr<float>(),
+        (int)f, (float)lambda, (float)alpha, implicit_mode ? 1 : 0,
+        wr_scale ? 1 : 0, stream);
+  else
   launch_als_heavy(
       reinterpret_cast<const long long*>(chunks.data_ptr<int64_t>()),
       reinterpret_cast<const long long*>(chunk_ptr.data_ptr<int64_t>()),
@@ -371,6 +409,78 @@ void als_heavy_solve(torch::Tensor indices, torch::Tensor values,
       carry.data_ptr<float>(), (int)f, (float)lambda, (float)alpha,
       implicit_mode ? 1 : 0, wr_scale ? 1 : 0, stream);
   C10_HIP_CHECK(hipGetLastError());
+}
+
+int* check_iters(const c10::optional<torch::Tensor>& iters,
+                 const torch::Tensor& X) {
+  if (!iters.has_value()) return nullptr;
+  TORCH_CHECK(iters->is_cuda() && iters->is_contiguous() &&
+                  iters->scalar_type() == torch::kInt32 &&
+                  iters->device() == X.device() &&
+                  iters->numel() == X.size(0),
+              "iters must be a contiguous i32 GPU tensor, one per row");
+  return iters->data_ptr<int>();
+}
+
+// The nonnegative half-step (als_nnls.hip): per row the minimiser of
+// 1/2 x^T A x - b^T x over x >= 0, A and b those of als_solve, by block
+// principal pivoting. Every row of degree <= skip_above is solved; rows
+// above it are left to als_heavy_solve(nonnegative = true). iters, if
+// given ([n_rows] i32), receives the solver's trip count per row.
+torch::Tensor als_nnls_solve(torch::Tensor indptr, torch::Tensor indices,
+                             torch::Tensor values, torch::Tensor Y,
+                             c10::optional<torch::Tensor> YtY,
+                             double lambda, double alpha,
+                             bool implicit_mode, bool wr_scale,
+                             c10::optional<torch::Tensor> out,
+                             int64_t skip_above,
+                             c10::optional<torch::Tensor> iters) {
+  TORCH_CHECK(skip_above > 0 && skip_above <= INT_MAX,
+              "skip_above must be in [1, INT_MAX]");
+  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt64 &&
+                  indptr.is_contiguous(), "indptr must be contiguous i64 GPU");
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+                  indices.is_contiguous(), "indices must be contiguous i32 GPU");
+  check_cuda_f32(values, "values");
+  check_cuda_f32(Y, "Y");
+  const int64_t f = Y.size(1);
+  TORCH_CHECK(supported_rank(f), "rank must be one of 16/32/64/128, got ", f);
+  const int64_t n_rows = indptr.size(0) - 1;
+  TORCH_CHECK(n_rows >= 0 && n_rows < INT_MAX, "row count must be below 2^31");
+  TORCH_CHECK(indices.size(0) == values.size(0), "indices/values mismatch");
+  // factor rows and YtY rows are read in 16-byte quads
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Y.data_ptr()) % 16 == 0,
+              "Y must be 16-byte aligned");
+  const float* yty_ptr = nullptr;
+  if (YtY.has_value()) {
+    check_cuda_f32(*YtY, "YtY");
+    TORCH_CHECK(YtY->size(0) == f && YtY->size(1) == f, "YtY must be f x f");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(YtY->data_ptr()) % 16 == 0,
+                "YtY must be 16-byte aligned");
+    yty_ptr = YtY->data_ptr<float>();
+  }
+  TORCH_CHECK(!implicit_mode || yty_ptr != nullptr,
+              "implicit mode needs YtY");
+  torch::Tensor X;
+  if (out.has_value()) {
+    check_cuda_f32(*out, "out");
+    TORCH_CHECK(out->size(0) == n_rows && out->size(1) == f,
+                "out must be n_rows x f");
+    X = *out;
+  } else {
+    X = torch::empty({n_rows, f}, Y.options());
+  }
+  int* iters_ptr = check_iters(iters, X);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  launch_als_nnls(
+      reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
+      indices.data_ptr<int>(), values.data_ptr<float>(), Y.data_ptr<float>(),
+      yty_ptr, X.data_ptr<float>(), iters_ptr, (int)n_rows, (int)f,
+      (float)lambda, (float)alpha, implicit_mode ? 1 : 0, wr_scale ? 1 : 0,
+      (int)skip_above, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return X;
 }
 
 // out[N, f] = in[N, f] . W[f, f] in exact fp32 on the matrix pipe (see
@@ -1033,7 +1143,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("YtY"), py::arg("X"), py::arg("rows"), py::arg("chunk_ptr"),
         py::arg("chunks"), py::arg("chunk_ptr_host"), py::arg("lambda_"),
         py::arg("alpha"), py::arg("implicit_mode"), py::arg("wr_scale"),
-        py::arg("ws_bytes") = (int64_t)256 << 20);
+        py::arg("ws_bytes") = (int64_t)256 << 20,
+        py::arg("nonnegative") = false, py::arg("iters") = py::none());
+  m.def("als_nnls_solve", &als_nnls_solve,
+        "Nonnegative ALS half-iteration: fused block-pivoting NNLS solve",
+        py::arg("indptr"), py::arg("indices"), py::arg("values"),
+        py::arg("Y"), py::arg("YtY") = py::none(),
+        py::arg("lambda_") = 0.01, py::arg("alpha") = 1.0,
+        py::arg("implicit_mode") = false, py::arg("wr_scale") = true,
+        py::arg("out") = py::none(),
+        py::arg("skip_above") = (int64_t)INT_MAX,
+        py::arg("iters") = py::none());
+  m.def("als_nnls_max_it", &als_nnls_max_it,
+        "Trip bound of the nonnegative solver");
   m.def("als_row_transform", &als_row_transform,
         "out[N, f] = in[N, f] . W[f, f], fp32 MFMA row transform",
         py::arg("in_"), py::arg("W"), py::arg("out") = py::none());

@@ -254,7 +254,8 @@ class ECommModel:
 
 class ECommAlgorithm(Algorithm):
     """Params: appName, unseenOnly, seenEvents, similarEvents, rank,
-    numIterations, lambda, alpha, [seed], [buyScore]."""
+    numIterations, lambda, alpha, [seed], [buyScore].
+    [nonnegative]: factors constrained to >= 0 (MLlib's setNonnegative)."""
 
     def train(self, pd: PreparedData) -> ECommModel:
         # Reference parity: ECommAlgorithm.genMLlibRating builds MLlib
@@ -319,7 +320,8 @@ class ECommAlgorithm(Algorithm):
             alpha=float(self.params.get("alpha", 1.0)),
             implicit=True, seed=self.params.get("seed"),
             loss_every=int(self.params.get("lossEvery", 0)),
-            tol=float(self.params.get("convergenceTol", 0.0)))
+            tol=float(self.params.get("convergenceTol", 0.0)),
+            nonnegative=bool(self.params.get("nonnegative", False)))
         device = pdist.compute_device()
         X, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)

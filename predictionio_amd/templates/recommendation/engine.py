@@ -243,7 +243,8 @@ class ALSModel(PersistentModel):
 class ALSAlgorithm(Algorithm):
     """Params: rank, numIterations, lambda, [alpha], [implicitPrefs],
     [seed] (engine.json `als` params in the reference template), plus
-    [lossEvery] and [convergenceTol] (ALSParams.loss_every / tol)."""
+    [lossEvery] and [convergenceTol] (ALSParams.loss_every / tol).
+    [nonnegative]: factors constrained to >= 0 (MLlib's setNonnegative)."""
 
     def train(self, pd: PreparedData) -> ALSModel:
         if pd.columns is not None and len(pd.columns):
@@ -293,7 +294,8 @@ class ALSAlgorithm(Algorithm):
             # optional: log the training objective every N iterations,
             # stop early once it improves by no more than the tolerance
             loss_every=int(self.params.get("lossEvery", 0)),
-            tol=float(self.params.get("convergenceTol", 0.0)))
+            tol=float(self.params.get("convergenceTol", 0.0)),
+            nonnegative=bool(self.params.get("nonnegative", False)))
         device = pdist.compute_device()
         X, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)

@@ -180,7 +180,8 @@ class SimilarModel:
 
 class ALSAlgorithm(Algorithm):
     """Params: rank, numIterations, lambda, alpha, [seed], [lossEvery],
-    [convergenceTol]."""
+    [convergenceTol].
+    [nonnegative]: factors constrained to >= 0 (MLlib's setNonnegative)."""
 
     def train(self, pd: PreparedData) -> SimilarModel:
         if not pd.view_events:
@@ -207,7 +208,8 @@ class ALSAlgorithm(Algorithm):
             alpha=float(self.params.get("alpha", 1.0)),
             implicit=True, seed=self.params.get("seed"),
             loss_every=int(self.params.get("lossEvery", 0)),
-            tol=float(self.params.get("convergenceTol", 0.0)))
+            tol=float(self.params.get("convergenceTol", 0.0)),
+            nonnegative=bool(self.params.get("nonnegative", False)))
         device = pdist.compute_device()
         _, Y = train_als(users, items, vals, len(user_map), len(item_map),
                          p, device=device)
