@@ -67,6 +67,14 @@ extern "C" void launch_topk_mfma(
     const int* item_cats, const int* query_cats, int cw, int interleave,
     const float* item_weights, hipStream_t stream);
 
+extern "C" void launch_topk_mfma_wide(
+    const unsigned short* Xq, const unsigned short* Y,
+    const uint8_t* item_mask, const long long* ban_indptr,
+    const int* ban_indices, float* out_val, int* out_idx,
+    int B, long long N, int f, int K, int n_slices, int item_base,
+    unsigned* th_g, const int* item_cats, const int* query_cats, int cw,
+    int interleave, const float* item_weights, hipStream_t stream);
+
 extern "C" void launch_topk_rescore(
     const float* Xq, const float* Y, const int* idx, const float* w,
     float* out, long long B, int C, int f, hipStream_t stream);
@@ -693,6 +701,68 @@ std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma(
   return {out_val, out_idx};
 }
 
+// topk_score_mfma for padded ranks 256 / 384 / 512 (topk_mfma_wide.hip:
+// the rank streamed through LDS in 128-wide panels). Same arguments, same
+// validation, same output layout; the wide kernel has no phase probe, so
+// a prof tensor raises.
+std::tuple<torch::Tensor, torch::Tensor> topk_score_mfma_wide(
+    torch::Tensor Xq, torch::Tensor Y, int64_t K, int64_t n_slices,
+    c10::optional<torch::Tensor> item_mask,
+    c10::optional<torch::Tensor> ban_indptr,
+    c10::optional<torch::Tensor> ban_indices, int64_t item_base,
+    c10::optional<torch::Tensor> prof,
+    c10::optional<torch::Tensor> item_cats,
+    c10::optional<torch::Tensor> query_cats, bool interleave,
+    c10::optional<bool> gth_opt,
+    c10::optional<torch::Tensor> item_weights) {
+  TORCH_CHECK(Xq.is_cuda() && Xq.is_contiguous() &&
+                  Xq.scalar_type() == torch::kBFloat16,
+              "Xq must be contiguous bf16 GPU");
+  TORCH_CHECK(Y.is_cuda() && Y.is_contiguous() &&
+                  Y.scalar_type() == torch::kBFloat16,
+              "Y must be contiguous bf16 GPU");
+  TORCH_CHECK(!prof.has_value(), "the wide-rank kernel has no phase probe");
+  const float* wts = check_item_weights(item_weights, Y, false);
+  TORCH_CHECK(Xq.dim() == 2 && Y.dim() == 2, "Xq and Y must be 2-D");
+  const int64_t f = Y.size(1);
+  TORCH_CHECK(f == 256 || f == 384 || f == 512,
+              "wide mfma rank must be one of 256/384/512, got ", f);
+  TORCH_CHECK(Xq.size(1) == f, "Xq/Y rank mismatch");
+  TORCH_CHECK(K >= 1 && K <= 64, "K must be in [1, 64]");
+  const int64_t B = Xq.size(0);
+  const int64_t N = Y.size(0);
+  TORCH_CHECK(n_slices >= 1);
+  const TopkArgs a = check_topk_args(item_mask, ban_indptr, ban_indices, prof,
+                                     item_cats, query_cats, B, N);
+  auto out_val = torch::empty({B, n_slices * K},
+                              Xq.options().dtype(torch::kFloat32));
+  auto out_idx = torch::empty({B, n_slices * K},
+                              Xq.options().dtype(torch::kInt32));
+  if (B == 0) return {out_val, out_idx};
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  hipStream_t stream =
+      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  // the cross-slice threshold cell, as in topk_score_mfma
+  torch::Tensor th_g;
+  unsigned* th_g_ptr = nullptr;
+  const char* e_gth = getenv("PIO_TOPK_GTH");
+  const bool gth = gth_opt.has_value()
+      ? *gth_opt : !(e_gth != nullptr && e_gth[0] == '0');
+  if (gth) {
+    th_g = torch::zeros({B}, Xq.options().dtype(torch::kInt32));
+    th_g_ptr = reinterpret_cast<unsigned*>(th_g.data_ptr<int>());
+  }
+  launch_topk_mfma_wide(
+      reinterpret_cast<const unsigned short*>(Xq.data_ptr()),
+      reinterpret_cast<const unsigned short*>(Y.data_ptr()), a.mask,
+      a.ban_indptr, a.ban_indices, out_val.data_ptr<float>(),
+      out_idx.data_ptr<int>(), (int)B, (long long)N, (int)f, (int)K,
+      (int)n_slices, (int)item_base, th_g_ptr, a.item_cats, a.query_cats,
+      a.cw, interleave ? 1 : 0, wts, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {out_val, out_idx};
+}
+
 // out[b, c] = dot(Xq[b, :], Y[idx[b, c], :]) in fp32, times
 // item_weights[idx[b, c]] when weights are given; idx < 0 gives -inf.
 // Any rank: rows move as float4 when f % 4 == 0 and both base pointers
@@ -1173,6 +1243,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("item_weights") = py::none());
   m.def("topk_score_mfma", &topk_score_mfma,
         "Fused masked top-K scoring on MFMA (bf16 in, fp32 accumulate)",
+        py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
+        py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
+        py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,
+        py::arg("prof") = py::none(), py::arg("item_cats") = py::none(),
+        py::arg("query_cats") = py::none(), py::arg("interleave") = false,
+        py::arg("gth") = py::none(), py::arg("item_weights") = py::none());
+  // the argument list of topk_score_mfma, position for position, so the
+  // Python call sites are shared; prof is accepted only to be refused
+  m.def("topk_score_mfma_wide", &topk_score_mfma_wide,
+        "topk_score_mfma for padded ranks 256 / 384 / 512 (rank panels)",
         py::arg("Xq"), py::arg("Y"), py::arg("K"), py::arg("n_slices") = 64,
         py::arg("item_mask") = py::none(), py::arg("ban_indptr") = py::none(),
         py::arg("ban_indices") = py::none(), py::arg("item_base") = 0,

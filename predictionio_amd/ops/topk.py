@@ -42,9 +42,10 @@ def bf16_copy(t: torch.Tensor, pad_to: Optional[int] = None) -> torch.Tensor:
 
 
 def _mfma_rank(f: int) -> Optional[int]:
-    """Padded rank for the MFMA kernel (K-dim multiples of 32), or None
-    when unsupported."""
-    for s in (32, 64, 128):
+    """Padded rank for the MFMA kernels, or None when unsupported: 32, 64
+    or 128 for topk_mfma_kernel, and 256, 384 or 512 (two to four 128-wide
+    rank panels) for topk_mfma_wide_kernel."""
+    for s in (32, 64, 128, 256, 384, 512):
         if f <= s:
             return s
     return None
@@ -81,6 +82,15 @@ def topk_score(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     top K is served whenever its bf16 rank among the valid items is at
     most D. "fp32" forces the all-fp32 VALU kernel (v3), which is exact.
     CPU ignores mode.
+
+    Rank: "mfma" serves any rank up to 512. Ranks up to 128 are padded to
+    32 / 64 / 128 and run topk_mfma_kernel; ranks 129..512 are padded to
+    256 / 384 / 512 and run topk_mfma_wide_kernel, which streams the rank
+    through LDS in 128-wide panels, with the same routes, filters, weights
+    and shortlist contract. Above 512 there is no fused kernel: K <= 64
+    raises ValueError and larger K takes the materialized fallback.
+    mode="fp32" keeps its limit of 128 (ValueError above), and so do
+    candidate lists.
 
     Eager "mfma" calls with K <= 1024 take the union path
     (_topk_score_union) when the shape has a plan for it: short
@@ -297,6 +307,18 @@ def _mfma_default_slices(B: int, N: int, pf: int, K: int, W: int,
     pass doubled the time (profiles/serve_k_sweep_r2.log). W = category
     words per item (0 = no filter); wt = item weights are staged."""
     ublocks = (B + 63) // 64
+    if pf > 128:
+        # tw_lds_bytes in csrc/topk_mfma_wide.hip: two 16 KB panel
+        # buffers at every rank, category words and weights staged twice;
+        # its registers allow 3 workgroups per CU (2 in some filtered or
+        # weighted rank-512 instantiations, which is not modelled)
+        lds = 2 * 64 * 256 + 8 * 64 * (K + 1) + 4 * 64
+        if W:
+            lds += 2 * W * (64 + (32 // W if W > 1 else 0)) * 4 + 64 * W * 4
+        if wt:
+            lds += 2 * 64 * 4
+        target = 256 * max(1, min(3, (160 * 1024) // lds))
+        return max(2, min(target // ublocks, (N + 255) // 256))
     # the kernel's dynamic LDS: tm_lds_bytes in csrc/topk_mfma.hip
     lds = 64 * 2 * pf + 8 * 64 * (K + 1) + 4 * 64
     if W:
@@ -429,6 +451,7 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
                       item_cats=None, query_cats=None, item_weights=None
                       ) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
     """Union path, the eager route at every K <= 1024: ONE MFMA launch
+    (topk_mfma_kernel, or topk_mfma_wide_kernel for ranks above 128)
     with short lists (L <= 64, the kernel's tuned regime) over S slices
     interleaved at chunk granularity, cross-slice threshold off; the
     S*L candidates are merged to the bf16 top M = 2K, re-scored exactly
@@ -452,7 +475,9 @@ def _topk_score_union(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     M = 2 * K
     ext = hip_ext()
     Xp = Xq if pf == f else torch.nn.functional.pad(Xq, (0, pf - f))
-    vals, idxs = ext.topk_score_mfma(
+    # ranks above 128: the rank-panel kernel, same arguments and output
+    launch = ext.topk_score_mfma_wide if pf > 128 else ext.topk_score_mfma
+    vals, idxs = launch(
         Xp.to(torch.bfloat16).contiguous(), bf16_copy(Y, pf), L, S,
         item_mask.contiguous() if item_mask is not None else None,
         ban_indptr.contiguous() if ban_indptr is not None else None,
@@ -546,7 +571,9 @@ def _topk_score_mfma(Xq: torch.Tensor, Y: torch.Tensor, K: int,
     # Y's bf16 copy is cached (factors are static across serving batches);
     # Xq is cast per call — it changes every batch, and under hipGraph
     # capture (GraphedTopK) the cast must be part of the captured work
-    vals, idxs = hip_ext().topk_score_mfma(
+    ext = hip_ext()
+    launch = ext.topk_score_mfma_wide if pf > 128 else ext.topk_score_mfma
+    vals, idxs = launch(
         Xp.to(torch.bfloat16).contiguous(), bf16_copy(Y, pf), depth,
         int(n_slices),
         item_mask.contiguous() if item_mask is not None else None,
