@@ -30,7 +30,10 @@ from predictionio_amd.parallel import dist as pdist
 
 @dataclass
 class ALSParams:
-    rank: int = 10
+    rank: int = 10              # up to 256 on GPU. Above 128 the solve is
+                                # the packed-triangle kernel (ops/csrc/
+                                # als_wide.hip); nonnegative, loss() /
+                                # loss_every / tol and heldout() stop at 128
     iterations: int = 10
     lambda_: float = 0.01
     alpha: float = 1.0          # implicit confidence weight
@@ -176,7 +179,8 @@ class ALSTrainer:
         indptr, indices, values = csr
         lv = None
         if (self.p.implicit and fixed_full.is_cuda
-                and not self.p.nonnegative):   # NNLS has no Woodbury form
+                and not self.p.nonnegative    # NNLS has no Woodbury form,
+                and self.p.rank <= 128):      # nor has the rank > 128 solver
             lv = als_ops.prepare_lv(fixed_full, yty, self.p.lambda_)
         step_rows = (g.max_rows + n_chunks - 1) // n_chunks
         for c in range(n_chunks):

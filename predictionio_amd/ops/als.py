@@ -22,6 +22,20 @@ def pad_rank(f: int) -> int:
     raise ValueError(f"rank {f} > 128 not supported")
 
 
+ALS_WIDE_RANKS = (192, 256)  # the packed-triangle solver (csrc/als_wide.hip)
+
+
+def als_pad_rank(f: int) -> int:
+    """The rank als_solve pads f to on a GPU: pad_rank up to 128, then 192
+    and 256. Only the ALS solve goes past 128; everything else that pads
+    (top-K fp32 mode, held-out ranking, the Woodbury precompute) keeps
+    pad_rank."""
+    for s in SUPPORTED_RANKS + ALS_WIDE_RANKS:
+        if f <= s:
+            return s
+    raise ValueError(f"rank {f} > 256 not supported by the ALS solvers")
+
+
 ROW_LIMIT = 2 ** 31  # the kernels carry row counts and row ids as int
 
 
@@ -269,10 +283,22 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
     ignored. On CPU: als_solve_nnls_ref. nnls_iters: optional int32 [rows]
     GPU tensor that receives the solver's trip count per row (a probe's
     output; needs nonnegative).
+
+    Ranks 129..256 on GPU are padded to 192 or 256 (als_pad_rank) and
+    take one pass of the packed-triangle MFMA solver (csrc/als_wide.hip)
+    over all rows, explicit or implicit: no Woodbury pass (lv is ignored)
+    and no heavy-row split (plan is ignored). nonnegative raises
+    ValueError there, and so does any rank above 256, before any copy or
+    launch. PIO_ALS_WIDE_GRID=N (read on every call) runs that solver on N
+    workgroups instead of one per CU; a row's bits do not depend on it.
     """
     if nnls_iters is not None and not (nonnegative and Y.is_cuda):
         raise ValueError("nnls_iters is an output of the GPU nonnegative "
                          "solver")
+    if Y.is_cuda:
+        if als_pad_rank(Y.shape[1]) > 128 and nonnegative:
+            raise ValueError(
+                f"nonnegative solves stop at rank 128, got {Y.shape[1]}")
     check_row_count(indptr=indptr.shape[0] - 1, Y=Y.shape[0])
     n_all = indptr.shape[0] - 1
     if implicit:
@@ -286,7 +312,7 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
         from predictionio_amd.ops import hip_ext
         ext = hip_ext()
         f = Y.shape[1]
-        pf = pad_rank(f)
+        pf = als_pad_rank(f)
         Yp = (Y if pf == f
               else torch.nn.functional.pad(Y, (0, pf - f))).contiguous()
         YtYp = None
@@ -305,6 +331,23 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
                 raise ValueError(
                     f"CSR column id out of range: [{int(ix.min())}, {mx}]"
                     f" vs {Y.shape[0]} factor rows")
+        direct_out = (out if out is not None and pf == f
+                      and out.is_contiguous() else None)
+        if pf > 128:
+            # one pass over every row: no Woodbury, no heavy-row split
+            if ip.numel() and (int(ip[0]) < 0 or int(ip[-1]) > ix.numel()):
+                raise ValueError(
+                    f"CSR row pointers [{int(ip[0])}, {int(ip[-1])}] outside"
+                    f" the {ix.numel()} stored ratings")
+            X = ext.als_solve_wide(
+                ip, ix, vv, Yp, YtYp, float(lam), float(alpha),
+                bool(implicit), bool(wr_scale), direct_out,
+                int(os.environ.get("PIO_ALS_WIDE_GRID", "0")))
+            res = X[:, :f].contiguous() if pf != f else X
+            if out is not None and res.data_ptr() != out.data_ptr():
+                out.copy_(res)
+                return out
+            return res
         # heavy rows: the dense kernels skip them, the split-row pass at
         # the end solves them
         hp = None
@@ -319,8 +362,6 @@ def als_solve(indptr: torch.Tensor, indices: torch.Tensor,
             if hp.rows.numel() == 0:
                 hp = None
         above = hmin if hp is not None else _INT_MAX
-        direct_out = (out if out is not None and pf == f
-                      and out.is_contiguous() else None)
         if nonnegative:
             X = ext.als_nnls_solve(ip, ix, vv, Yp, YtYp, float(lam),
                                    float(alpha), bool(implicit),

@@ -20,7 +20,8 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
            "als_loss.hip", "topk_kernels.hip", "topk_mfma.hip", "topk_rescore.hip",
            "cooc_topn.hip", "topk_cand.hip", "indicator_topk.hip",
            "rank_count.hip", "topk_kernels_wt.hip", "topk_mfma_wt.hip",
-           "als_heavy.hip", "als_nnls.hip", "topk_mfma_wide.hip"]
+           "als_heavy.hip", "als_nnls.hip", "topk_mfma_wide.hip",
+           "als_wide.hip"]
 # compiled on their own with packed fp32 VALU ops off (the vectorizer may
 # otherwise pair independent fp32 chains), then linked with the rest.
 # cooc_topn.hip is here since its LLR score stage: today it holds no
@@ -42,10 +43,12 @@ SOURCES = ["bindings.cpp", "als_kernels.hip", "als_xform.hip",
 # its Cholesky, substitutions and gradient must not be re-associated.
 # topk_mfma_wide.hip: holds its weighted (WT = true) instantiations too,
 # whose weight products must stay single fp32 ops like topk_mfma_wt.hip's.
+# als_wide.hip: als_heavy.hip's reasons (weight products feeding MFMAs),
+# and the ordered fma chains of its panel solve and substitutions.
 NO_PACKED_FP32 = ["topk_cand.hip", "cooc_topn.hip", "indicator_topk.hip",
                   "rank_count.hip", "topk_kernels_wt.hip",
                   "topk_mfma_wt.hip", "als_heavy.hip", "als_nnls.hip",
-                  "topk_mfma_wide.hip"]
+                  "topk_mfma_wide.hip", "als_wide.hip"]
 HEADERS = ["topk_common.h"]  # included by SOURCES: rebuild when they change
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

@@ -19,6 +19,14 @@ extern "C" void launch_als_solve(
     int implicit_mode, int wr_scale, int which,
     unsigned long long* prof, int heavy_min, hipStream_t stream);
 
+extern "C" int als_wide_lds_bytes(int f);
+
+extern "C" void launch_als_solve_wide(
+    const long long* indptr, const int* indices, const float* values,
+    const float* Y, const float* YtY, float* X, int n_rows, int f,
+    float lambda, float alpha, int implicit_mode, int wr_scale,
+    int skip_below, int skip_above, int grid, hipStream_t stream);
+
 extern "C" long long als_heavy_slot_floats(int f);
 
 extern "C" void launch_als_heavy(
@@ -319,6 +327,64 @@ torch::Tensor als_solve(torch::Tensor indptr, torch::Tensor indices,
                    v_ptr, X.data_ptr<float>(), (int)n_rows, (int)f, (float)lambda,
                    (float)alpha, implicit_mode ? 1 : 0, wr_scale ? 1 : 0,
                    (int)which, prof_ptr, (int)heavy_min, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return X;
+}
+
+// The dense solve at the padded ranks 192 and 256 (als_wide.hip): every row
+// of the CSR in one pass, one 512-thread workgroup per row on `grid`
+// persistent workgroups (0: one per CU, which is what the LDS admits).
+// Same systems as als_solve; there is no Woodbury pass and no heavy-row
+// split at these ranks.
+torch::Tensor als_solve_wide(torch::Tensor indptr, torch::Tensor indices,
+                             torch::Tensor values, torch::Tensor Y,
+                             c10::optional<torch::Tensor> YtY,
+                             double lambda, double alpha, bool implicit_mode,
+                             bool wr_scale, c10::optional<torch::Tensor> out,
+                             int64_t grid) {
+  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt64 &&
+                  indptr.is_contiguous(), "indptr must be contiguous i64 GPU");
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+                  indices.is_contiguous(), "indices must be contiguous i32 GPU");
+  check_cuda_f32(values, "values");
+  check_cuda_f32(Y, "Y");
+  const int64_t f = Y.size(1);
+  TORCH_CHECK_VALUE(f == 192 || f == 256,
+                    "rank must be padded to 192 or 256, got ", f);
+  TORCH_CHECK(indptr.size(0) >= 1, "indptr must hold n_rows + 1 entries");
+  const int64_t n_rows = indptr.size(0) - 1;
+  TORCH_CHECK(n_rows <= INT_MAX, "row counts must be below 2^31");
+  TORCH_CHECK(indices.size(0) == values.size(0), "indices/values mismatch");
+  TORCH_CHECK_VALUE(!implicit_mode || YtY.has_value(),
+                    "implicit mode needs YtY");
+  TORCH_CHECK(grid >= 0 && grid <= (1 << 20), "grid must be in [0, 2^20]");
+  const float* yty_ptr = nullptr;
+  if (YtY.has_value()) {
+    check_cuda_f32(*YtY, "YtY");
+    TORCH_CHECK(YtY->size(0) == f && YtY->size(1) == f, "YtY must be f x f");
+    yty_ptr = YtY->data_ptr<float>();
+  }
+  torch::Tensor X;
+  if (out.has_value()) {
+    check_cuda_f32(*out, "out");
+    TORCH_CHECK(out->size(0) == n_rows && out->size(1) == f,
+                "out must be n_rows x f");
+    X = *out;
+  } else {
+    X = torch::empty({n_rows, f}, Y.options());
+  }
+  if (n_rows == 0) return X;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Y.device());
+  hipStream_t stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  if (grid == 0)
+    grid = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  grid = std::min<int64_t>(grid, n_rows);
+  launch_als_solve_wide(
+      reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
+      indices.data_ptr<int>(), values.data_ptr<float>(), Y.data_ptr<float>(),
+      yty_ptr, X.data_ptr<float>(), (int)n_rows, (int)f, (float)lambda,
+      (float)alpha, implicit_mode ? 1 : 0, wr_scale ? 1 : 0, -1, INT_MAX,
+      (int)grid, stream);
   C10_HIP_CHECK(hipGetLastError());
   return X;
 }
@@ -1207,6 +1273,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wr_scale") = true, py::arg("which") = 0,
         py::arg("out") = py::none(), py::arg("prof") = py::none(),
         py::arg("heavy_min") = (int64_t)INT_MAX);
+  m.def("als_solve_wide", &als_solve_wide,
+        "Dense ALS half-iteration at padded ranks 192 / 256 (MFMA solver)",
+        py::arg("indptr"), py::arg("indices"), py::arg("values"),
+        py::arg("Y"), py::arg("YtY") = py::none(), py::arg("lambda_") = 0.01,
+        py::arg("alpha") = 1.0, py::arg("implicit_mode") = false,
+        py::arg("wr_scale") = true, py::arg("out") = py::none(),
+        py::arg("grid") = (int64_t)0);
+  m.def("als_wide_lds_bytes", &als_wide_lds_bytes,
+        "LDS bytes per workgroup of the rank-192 / 256 solver");
   m.def("als_heavy_solve", &als_heavy_solve,
         "Split-row ALS solve of heavy rows: MFMA partial Gramians per chunk",
         py::arg("indices"), py::arg("values"), py::arg("Y"),
